@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: aligned bases/s of pileup + consensus on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
 
 A step = one full pass of the hot path (Steps 4-6 of the reference: cs parse
 -> pileup -> consensus calls) over one batch of synthetic, seeded,
@@ -24,7 +24,21 @@ parse -- a stream of plasmid batches as a sequencing run produces them.  Every
 step is still one full pass of the hot path over one batch; value = aligned
 bases of all K steps / wall time.  --inflight 1 runs them one after another.
 
-Output: one JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given, and prints the result line (metric, value, unit,
+ms_per_step, the workload).  Everything else measured here takes runs of its
+own and is behind --full.
+
+--dump-outputs DIR: after the timed steps, the calls the last timed step's
+pipeline holds, as its caller fetches them (Runner.fetch()), written by rank 0
+as DIR/sample<s>_<field>.npy (float64; field = base, chrom1, chrom2, count,
+count2, total, one element per call row of sample s) and DIR/max_depth.npy
+(one element per sample); over 64 MB in all, a fixed seeded sample of every
+sample's rows (DIR/sample<s>_rows.npy holds their indices).  The input is
+seeded, so the same arguments give the same files from any build.
+
+Output: one JSON line (rank 0) with the contract fields plus, with --full,
+  single_batch_ms_per_step  the same config one batch at a time
   roofline      the dominant kernel (K_parse) vs the HBM roofline: algorithmic
                 bytes (sum of cs bytes + 24 B per read) / its mean
                 duration measured here with HIP events on the launch stream;
@@ -268,6 +282,40 @@ def traffic_record(cfg, world):
     return None, None
 
 
+DUMP_FIELDS = ("base", "chrom1", "chrom2", "count", "count2", "total")
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, results):
+    """Write a step's fetched calls (a list of per-sample dicts, Runner.fetch())
+    as float64 .npy files under ``out_dir``: sample<s>_<field>.npy per sample
+    and field of DUMP_FIELDS, max_depth.npy over the samples.  Above
+    DUMP_MAX_BYTES in all, every sample keeps the same fixed fraction of its
+    rows, drawn with a fixed seed (sorted; their indices in sample<s>_rows.npy).
+    Returns the bytes of array data written."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = sum(len(r["base"]) for r in results)
+    per_row = 8 * (len(DUMP_FIELDS) + 1)  # the fields and, if sampled, the row index
+    budget = DUMP_MAX_BYTES - 8 * len(results) - (1 << 20)  # max_depth and the .npy headers
+    keep = 1.0 if rows * per_row <= budget else budget / (rows * per_row)
+    rng = np.random.default_rng(DUMP_SEED)
+    written = 0
+    for s, r in enumerate(results):
+        n = len(r["base"])
+        idx = None
+        if keep < 1.0:
+            idx = np.sort(rng.choice(n, size=int(n * keep), replace=False))
+            np.save(os.path.join(out_dir, f"sample{s}_rows.npy"), idx.astype(np.float64))
+            written += 8 * len(idx)
+        for f in DUMP_FIELDS:
+            a = np.asarray(r[f]) if idx is None else np.asarray(r[f])[idx]
+            np.save(os.path.join(out_dir, f"sample{s}_{f}.npy"), a.astype(np.float64))
+            written += 8 * len(a)
+    np.save(os.path.join(out_dir, "max_depth.npy"), np.array([r["max_depth"] for r in results], dtype=np.float64))
+    return written + 8 * len(results)
+
+
 def launch_ranks(n, argv):
     """``bench.py --gpus N`` (N > 1) started WITHOUT a launcher: run the same
     command as N rank processes (one per GPU) under torch.distributed.run, as a
@@ -323,10 +371,16 @@ def main():
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto", nargs="?", const="on",
                     help="distributed path: replay every pipeline's step from a HIP graph (no host dispatch); "
                          "auto = on for RCCL at world size > 1; a bare --graph = on")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the calls of the last timed step as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the single-batch step, the K_parse rooflines "
+                         "(--kernel-reps, --hbm-config), the CPU baseline and the end-to-end CLI")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end CLI timing")
     ap.add_argument("--hbm-config", default="c3", type=lambda s: s.strip().lower(),
-                    help="also time K_parse on this (L3-exceeding) config for the HBM roofline; "
+                    help="with --full: also time K_parse on this (L3-exceeding) config for the HBM roofline; "
                          "'' or 'none' to skip")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
@@ -497,6 +551,47 @@ def main():
     ms = dt * 1e3 / args.steps
     value = aligned * args.steps / dt
 
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step computed: the calls its pipeline holds, as its
+        # caller fetches them (every rank holds the global result; c5: rank 0's plasmids)
+        last = runners[(args.steps - 1) % R]
+        last.check()
+        res = last.fetch()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, res)
+        del res, last
+
+    line = {
+        "metric": METRIC, "value": value, "unit": "aligned bases/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
+        "scaling": "strong" if scaling == "strong" else "weak",
+        "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic: seeded cs-tag generator (SURVEY §8(d) profile), device-resident",
+        "config": {"workload": desc, "ref_len": n, "global_reads_per_sample": global_reads,
+                   "local_reads": int(len(samples[0]["tstart"])), "samples_per_gpu": len(samples),
+                   "profile": profile, "aligned_bases_per_step": aligned,
+                   "cs_bytes_gpu0": int(sum(int(s["cs_off"][-1] - s["cs_off"][0]) for s in samples)),
+                   "min_depth_factor": mdf, "global_threshold_factor": gtf,
+                   "parallelism": ("replicas" if cfg == "c5" else "read-shard") + f"x{world}",
+                   "batches_in_flight": R, "parse_cus": cus or 256,
+                   "process_group": backend if use_dist else None, "graph": graph_note},
+        "full": args.full,
+        "what": ("value = aligned bases of K steps / wall time with %d batch copies in flight on %d streams "
+                 "(pipelined throughput)" % (R, R)
+                 if R > 1 else "value = aligned bases of K steps / wall time, one batch at a time"),
+    }
+    if args.dump_outputs:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
+    if not args.full:
+        # a plain run: the headline figure only
+        line["config"]["parse_geometry_timed"] = runners[0].plan.info()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
     def kparse_ms(plan, reps, stream, beside=None):
         """Mean K_parse launch (HIP events on its own stream); ``beside``: a step
         of another pipeline enqueued on its stream before each launch."""
@@ -585,24 +680,10 @@ def main():
         e2e = e2e_cli(pkg, cfg)
 
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": value, "unit": "aligned bases/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
-            "scaling": "strong" if scaling == "strong" else "weak",
-            "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic: seeded cs-tag generator (SURVEY §8(d) profile), device-resident",
-            "config": {"workload": desc, "ref_len": n, "global_reads_per_sample": global_reads,
-                       "local_reads": int(len(samples[0]["tstart"])), "samples_per_gpu": len(samples),
-                       "profile": profile, "aligned_bases_per_step": aligned,
-                       "cs_bytes_gpu0": int(sum(int(s["cs_off"][-1] - s["cs_off"][0]) for s in samples)),
-                       "min_depth_factor": mdf, "global_threshold_factor": gtf,
-                       "parallelism": ("replicas" if cfg == "c5" else "read-shard") + f"x{world}",
-                       "batches_in_flight": R, "parse_cus": cus or 256,
-                       "process_group": backend if use_dist else None, "graph": graph_note},
+        if R > 1:
+            line["what"] += "; single_batch_ms_per_step = the same config one batch at a time"
+        line.update({
             "single_batch_ms_per_step": single_ms,
-            "what": ("value = aligned bases of K steps / wall time with %d batch copies in flight on %d streams "
-                     "(pipelined throughput); single_batch_ms_per_step = the same config one batch at a time" % (R, R)
-                     if R > 1 else "value = aligned bases of K steps / wall time, one batch at a time"),
             "roofline": {"bound": ROOF_BOUND, "kernel": "K_parse", "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_record": traffic_src,
@@ -618,7 +699,7 @@ def main():
             "roofline_hbm": hbm,
             "cpu_baseline": cpu,
             "e2e": e2e,
-        }
+        })
         line["config"]["parse_geometry"] = geo
         print(json.dumps(line), flush=True)
     if use_dist:

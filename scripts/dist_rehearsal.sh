@@ -6,7 +6,7 @@ cd $R && mkdir -p gpurun_out
 N=${1:-2}
 CFG=${2:-c2}
 MPC_DIST_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --config $CFG --steps 5 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $N --config $CFG --steps 5 --warmup 2 \
   > gpurun_out/dist_$N.log 2>&1
 rc=$?
 tail -4 gpurun_out/dist_$N.log

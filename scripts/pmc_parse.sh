@@ -12,6 +12,6 @@ for P in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_
          "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_ATOMIC_sum TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $P -d $OUT/p$i -o run --output-format csv -- \
-    python3 $R/bench.py --config $CFG --steps 3 --warmup 1 --kernel-reps 3 --no-cpu-baseline > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
+    python3 $R/bench.py --full --config $CFG --steps 3 --warmup 1 --kernel-reps 3 --no-cpu-baseline > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
 done
 echo done

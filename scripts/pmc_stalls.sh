@@ -17,7 +17,7 @@ for P in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_AN
   i=$((i+1))
   case $PASSES in *$i*) ;; *) continue ;; esac
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $P -d $OUT/p$i -o run --output-format csv -- \
-    python3 $R/bench.py --config $CFG --steps 2 --warmup 1 --kernel-reps 2 --no-cpu-baseline --no-e2e --hbm-config "" > $OUT/p$i.log 2>&1 \
+    python3 $R/bench.py --full --config $CFG --steps 2 --warmup 1 --kernel-reps 2 --no-cpu-baseline --no-e2e --hbm-config "" > $OUT/p$i.log 2>&1 \
     || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
 done
 python3 $R/scripts/pmcsum.py $OUT $KN | tee $OUT/summary.txt

@@ -97,6 +97,64 @@ def test_hbm_config_validated(monkeypatch):
     assert e.value.code == 2
 
 
+def _fake_results(rows=(7, 0, 1000)):
+    import numpy as np
+    rng = np.random.default_rng(3)
+    out = []
+    for s, n in enumerate(rows):
+        r = {k: rng.integers(0, 250, n).astype(np.uint8) for k in ("base", "chrom1", "chrom2")}
+        r.update({k: rng.integers(0, 1 << 40, n).astype(np.int64) for k in ("count", "count2", "total")})
+        r["max_depth"] = 1000 + s
+        r["raw"] = np.zeros((n, 4), dtype=np.uint32)
+        out.append(r)
+    return out
+
+
+def test_dump_outputs_writes_every_field(tmp_path):
+    """--dump-outputs: every field of every sample's calls as a float64 .npy
+    holding exactly the fetched values, max_depth over the samples."""
+    import numpy as np
+    bench = _bench()
+    res = _fake_results()
+    d = tmp_path / "new" / "dir"
+    nbytes = bench.dump_outputs(str(d), res)
+    names = sorted(os.listdir(d))
+    assert names == sorted([f"sample{s}_{f}.npy" for s in range(3) for f in bench.DUMP_FIELDS] + ["max_depth.npy"])
+    total = 0
+    for s, r in enumerate(res):
+        for f in bench.DUMP_FIELDS:
+            a = np.load(d / f"sample{s}_{f}.npy")
+            assert a.dtype == np.float64 and a.shape == (len(r[f]),)
+            assert np.array_equal(a.astype(np.int64), np.asarray(r[f], dtype=np.int64))
+            total += a.nbytes
+    md = np.load(d / "max_depth.npy")
+    assert md.dtype == np.float64 and md.tolist() == [1000.0, 1001.0, 1002.0]
+    assert nbytes == total + md.nbytes
+
+
+def test_dump_outputs_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    """Above the size limit every sample keeps the same seeded rows in every
+    field, run after run, and the files stay within the limit."""
+    import numpy as np
+    bench = _bench()
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    res = _fake_results(rows=(40_000, 5, 90_000))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 << 20)
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert bench.dump_outputs(str(a), res) == bench.dump_outputs(str(b), res)
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= 3 << 20
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b))
+    for f in os.listdir(a):
+        assert np.array_equal(np.load(a / f), np.load(b / f)), f
+    for s, r in enumerate(res):
+        idx = np.load(a / f"sample{s}_rows.npy").astype(np.int64)
+        assert len(idx) < len(r["base"]) and np.all(np.diff(idx) > 0)
+        for f in bench.DUMP_FIELDS:
+            got = np.load(a / f"sample{s}_{f}.npy")
+            assert np.array_equal(got.astype(np.int64), np.asarray(r[f], dtype=np.int64)[idx]), (s, f)
+    assert len(np.load(a / "sample2_rows.npy")) > 10_000  # a sample, not a stub
+
+
 def test_reference_baseline_is_the_fastest_run():
     """cpu_baseline (kind reference) reports the minimum wall of its repeats
     (VERDICT r04 item 7), and says so in its sample text."""

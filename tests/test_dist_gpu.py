@@ -224,7 +224,7 @@ def test_bench_self_launch_two_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MPC_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--config", "c2", "--steps", "3",
-           "--warmup", "1", "--kernel-reps", "2", "--inflight", "2", "--hbm-config", ""]
+           "--warmup", "1", "--full", "--kernel-reps", "2", "--inflight", "2", "--hbm-config", ""]
     p = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=540)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
