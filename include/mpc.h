@@ -40,7 +40,10 @@
 extern "C" {
 #endif
 
-#define MPC_ABI_VERSION 9  /* 9: mpc_plan_info.deferred_placement (struct grew) */
+#define MPC_ABI_VERSION 9  /* 9: mpc_plan_info.deferred_placement (struct grew).  Added since without a new
+                              number, because nothing a version-9 caller uses changed: mpc_wrap() and the
+                              MPC_BUF_WRAP_* buffers (negative starts with n_shards > 1; mpc_input keeps
+                              its 24 fields, a caller that never shards never meets them) */
 
 /* return codes */
 #define MPC_OK 0
@@ -59,7 +62,8 @@ extern "C" {
 #define MPC_DE_UNSUPPORTED 64u /* input the reference accepts but this engine does not: a ':' / '-' advance
                                   of 2^22 or more from a negative coordinate; tstart < MPC_TSTART_MIN; a
                                   write into a wrapped ODD position (below) in a plan that declared no
-                                  negative starts (mpc_input.neg_reads = 0) or with n_shards > 1 */
+                                  negative starts (mpc_input.neg_reads = 0; with n_shards > 1: no shard
+                                  declared one), or more such strings than the list bound (2^22) */
 
 /* Lowest target start the engine takes.  Negative starts (minimap2 never
  * writes one) follow the reference's Python negative indexing (:222,
@@ -69,8 +73,10 @@ extern "C" {
  * (:303, :81-87 -> obsarr[2i] = odd position n + i) and the downstream flank of
  * a read ending there (:323) add slots to a reference-base position: its
  * slot list is replayed like a gap's (:37-72) over those strings and the
- * one-base writes of the reads covering it, in read order (single shard;
- * the plan sizes the event list from mpc_input.neg_reads / neg_cs_bytes). */
+ * one-base writes of the reads covering it, in read order (the plan sizes
+ * the event list from mpc_input.neg_reads / neg_cs_bytes).  With n_shards > 1
+ * the shards exchange those strings as records (MPC_BUF_WRAP_REC -> _ALL) and
+ * every shard replays all of them in global read order (mpc_wrap). */
 #ifndef MPC_TSTART_MIN
 #define MPC_TSTART_MIN (-(1 << 28))
 #endif
@@ -135,7 +141,10 @@ typedef struct {
   /* reads with tstart < 0 and their cs bytes (host counts; 0, 0 when there
    * are none).  They bound the strings Python's negative wrap writes into odd
    * positions (upstream / downstream flanks, '+' insertions at i in [-n, 0));
-   * a plan sized with 0 reports such a write as MPC_DE_UNSUPPORTED. */
+   * a plan sized with 0 reports such a write as MPC_DE_UNSUPPORTED.  With
+   * n_shards > 1 both are the TOTALS over all shards, the same on every shard:
+   * every shard then plans the same K_parse, list capacity and layout kernel,
+   * and the two extra collectives line up on shards without a negative start. */
   int64_t neg_reads;
   int64_t neg_cs_bytes;
 } mpc_input;
@@ -158,6 +167,15 @@ enum {
   MPC_BUF_RUN_R,        /* int32[n_reads_global + gaps] length of the RIGHT event closing each run (MAX, span) */
   MPC_BUF_DIFF,         /* int32[gaps] this shard's read-span/deletion difference array (not exchanged)    */
   MPC_BUF_SUB,          /* uint32[gaps][4] this shard's substitution tallies        (not exchanged)        */
+  /* n_shards > 1 in a plan with negative starts (count 0 otherwise).  cap = the plan's list capacity, from
+   * neg_reads / neg_cs_bytes, the same on every shard.  A record is 6 int32: position g, global read, string
+   * length, kind, owning shard, index in the owner's list. */
+  MPC_BUF_WRAP_REC,     /* int32[cap][6] this shard's strings; the first min(status[MPC_ST_WRAP_EVENTS], cap)
+                           are valid after mpc_parse                                 (exchange: all-gather) */
+  MPC_BUF_WRAP_ALL,     /* int32[1 + cap][6] record 0 = {records behind it, 0...}, written by the host; then
+                           every shard's valid records, in shard order               (exchange: target)     */
+  MPC_BUF_WRAP_COVER,   /* int32[2 cap + 1] per run of a wrapped odd position: some read of this shard has a
+                           one-base write in it; runs <= 2 x the gathered records    (exchange: MAX)        */
   MPC_BUF_COUNT
 };
 
@@ -226,10 +244,12 @@ int mpc_plan_set_input(mpc_plan* plan, const mpc_input* in);
 /* Phases (single GPU: mpc_run() = all of them, in this order).  With
  * n_shards > 1 the host inserts these collectives (Multi-GPU):
  *   mpc_parse    ; OR  HASLEFT
+ *                ; negative starts only: ALL-GATHER the valid records of WRAP_REC -> WRAP_ALL (+ header)
  *   mpc_index    ; ALL-GATHER RIGHT_CNT -> RIGHT_CNT_ALL
  *   mpc_runs     (global run index space, RIGHT length per run)
  *   mpc_tally    ; MAX over the span MAXR .. RUN_R (MAXR, RUN_M, RUN_R lie in this order
  *                  in the workspace, with padding between them: one collective)
+ *   mpc_wrap     ; negative starts only: MAX WRAP_COVER[: 2 x gathered records + 1]
  *   mpc_layout   (identical on every shard)
  *   mpc_rows     ; SUM ROWS  (every shard's rows hold its own reads' counts, odd
  *                  positions included: DIFF / SUB are never exchanged)
@@ -238,6 +258,9 @@ int mpc_parse(mpc_plan* plan, void* stream);        /* clear; cs -> i_end, LEFT 
 int mpc_index(mpc_plan* plan, void* stream);        /* downstream (RIGHT) events at mixed gaps, stable (gap, read) sort; insertion work units */
 int mpc_runs(mpc_plan* plan, void* stream);         /* shards > 1: global run index space            */
 int mpc_tally(mpc_plan* plan, void* stream);        /* longest LEFT string per run (M)               */
+int mpc_wrap(mpc_plan* plan, void* stream);         /* shards > 1 with negative starts: runs of the wrapped odd positions over
+                                                       all shards' strings, this shard's one-base writes in them; else a
+                                                       no-op (one shard: mpc_layout does it; mpc_run is unchanged) */
 int mpc_layout(mpc_plan* plan, void* stream);       /* per-gap replay of the slot layout, row counts, row offsets, depth, odd rows */
 int mpc_rows(mpc_plan* plan, void* stream);         /* insertion and flank tallies onto the slot rows */
 int mpc_consensus(mpc_plan* plan, double min_depth_factor, double global_threshold_factor,

@@ -200,6 +200,19 @@ struct WoRun {
   uint32_t C[4];        // one-base LEFT writes of the reads covering the position (:79, :96)
 };
 constexpr int64_t kWoCapMax = 1 << 22;  // event list bound (the single-workgroup sort)
+// What a shard sends of a WoEv (n_shards > 1, K_wopack): nothing in it points
+// into the owner's buffers.  A flank's length comes from the owner's up_off /
+// down_off, which no other shard holds, so it travels here.  Record 0 of the
+// gathered list is a header: its g is the number of records behind it.
+struct WoRec {
+  int32_t g;      // as WoEv
+  int32_t gread;  // global read: read_offset + local read (< 2^30)
+  int32_t len;    // string length (flanks included)
+  int32_t type;   // kWo*
+  int32_t shard;  // the owner
+  int32_t ev;     // index in the owner's WoEv list
+};
+static_assert(sizeof(WoRec) == 24, "exchanged as 6 int32 (mpc.h MPC_BUF_WRAP_REC)");
 
 // Insertion events (what K_left reads): 4 bytes, bases (8 bits, 2 per base in
 // string order) | (len-1) << 8 | gap within its kBW-gap bucket << 10 | read
@@ -265,9 +278,26 @@ struct Dev {  // device-side views of the plan for the small kernels (passed by 
   int32_t* srow;                     // [S] first row of every sample (K_layout)
   // strings in wrapped odd positions (negative starts; wo_cap 0: none planned)
   WoEv* wo; uint64_t* wo_key; uint32_t* wo_idx; int32_t* wo_erun; WoPos* wo_pos; WoRun* wo_run;
-  int64_t wo_cap, wo_p2;             // list capacity, its power-of-two sort size
+  int64_t wo_cap;                    // list capacity
+  // n_shards > 1 with negative starts (else null): the three exchange buffers
+  // (wo_rec, wo_all, wo_cov below), laid out one after the other.  ONE pointer,
+  // in the place of a size no kernel read: Dev keeps its size and offsets, so
+  // the kernels that know nothing of this are compiled to what they were.
+  uint8_t* wo_x;
   double mdf, gtf;
 };
+static_assert(sizeof(void*) == sizeof(int64_t), "Dev layout");
+// this shard's records; all shards' records behind a header; per run "some
+// read of this shard has a one-base write" (each starts 256-byte aligned)
+__host__ __device__ inline int64_t wo_a256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+__device__ __forceinline__ WoRec* wo_rec(const Dev& d) { return reinterpret_cast<WoRec*>(d.wo_x); }
+__device__ __forceinline__ const WoRec* wo_all(const Dev& d) {
+  return reinterpret_cast<const WoRec*>(d.wo_x + wo_a256(d.wo_cap * (int64_t)sizeof(WoRec)));
+}
+__device__ __forceinline__ int32_t* wo_cov(const Dev& d) {
+  return reinterpret_cast<int32_t*>(d.wo_x + wo_a256(d.wo_cap * (int64_t)sizeof(WoRec)) +
+                                    wo_a256((d.wo_cap + 1) * (int64_t)sizeof(WoRec)));
+}
 
 // Dict code of a written base after .upper() (:87, :96): A0 T1 C2 G3, -1 if not ACGT.
 // (c|0x20) maps exactly {A,a}->a, {C,c}->c, {G,g}->g, {T,t}->t; h=(lc>>1)&3 is a
@@ -2835,6 +2865,13 @@ __global__ __launch_bounds__(UB) __attribute__((amdgpu_waves_per_eu(UB == 1024 ?
 //   K_layout<true> replays each listed position's runs (F slots, F rows)
 //   K_worows       the strings and the one-base counts onto those rows
 // None of it runs in plans without negative starts (mpc_input.neg_reads).
+// Several shards: K_wopack turns each shard's list into records that are
+// gathered (mpc.h MPC_BUF_WRAP_ALL); K_woprep then runs on the gathered list on
+// every shard -- the same positions, runs, M and R everywhere -- while
+// K_wocover and K_worows count only the shard's own reads and strings (the
+// rows are summed), and "the run has a one-base write", which K_layout<true>
+// needs of ALL reads, is a flag reduced over the shards (MPC_BUF_WRAP_COVER)
+// that K_wofold enters into the run's longest LEFT string.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t wo_sort_key(const WoEv& e) {
   return ((uint64_t)(uint32_t)e.g << 32) | ((uint64_t)(uint32_t)e.read << 2) | (uint64_t)(uint32_t)e.type;
@@ -2877,9 +2914,39 @@ __device__ __forceinline__ int32_t wo_len(const Dev& d, const WoEv& e) {
   return L > 0x7fffffff ? 0x7fffffff : (int32_t)L;
 }
 
+// strings in the list the replay runs over: this shard's own (one shard), or
+// every shard's, gathered behind the header record (the same on every shard)
+__device__ __forceinline__ int64_t wo_listed(const Dev& d) {
+  const int64_t n = d.wo_x ? (int64_t)wo_all(d)[0].g : (int64_t)d.status[MPC_ST_WRAP_EVENTS];
+  return n < d.wo_cap ? n : d.wo_cap;
+}
+__device__ __forceinline__ uint64_t wo_rec_key(const WoRec& e) {
+  return ((uint64_t)(uint32_t)e.g << 32) | ((uint64_t)(uint32_t)e.gread << 2) | (uint64_t)(uint32_t)e.type;
+}
+
+// n_shards > 1, after K_parse: this shard's strings as exchange records
+__global__ __launch_bounds__(256) void K_wopack(Dev d) {
+  const int64_t n = min<int64_t>((int64_t)d.status[MPC_ST_WRAP_EVENTS], d.wo_cap);
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const WoEv ev = d.wo[k];
+    WoRec r;
+    r.g = ev.g; r.gread = (int32_t)(d.read_offset + ev.read); r.len = wo_len(d, ev); r.type = ev.type;
+    r.shard = d.shard; r.ev = (int32_t)k;
+    wo_rec(d)[k] = r;
+  }
+}
+
 __global__ __launch_bounds__(1024) void K_woprep(Dev d) {
   __shared__ int32_t s_w[16];
-  const int64_t n = min<int64_t>((int64_t)d.status[MPC_ST_WRAP_EVENTS], d.wo_cap);
+  const bool sh = d.wo_x != nullptr;  // the gathered list: keys by global read, lengths from the records
+  const WoRec* all = wo_all(d);
+  int32_t* cov = wo_cov(d);
+  const int64_t n = wo_listed(d);
+  if (sh) {
+    // more strings than the list bound holds (kWoCapMax): as on one shard
+    if (threadIdx.x == 0 && (int64_t)all[0].g > d.wo_cap) atomicOr(&d.status[MPC_ST_FLAGS], DE_UNSUP);
+    for (int64_t k = threadIdx.x; k < 2 * n + 1; k += blockDim.x) cov[k] = 0;  // (runs <= 2 n)
+  }
   if (n == 0) {
     if (threadIdx.x == 0) d.status[MPC_ST_WRAP_POS] = 0u;
     return;
@@ -2889,7 +2956,7 @@ __global__ __launch_bounds__(1024) void K_woprep(Dev d) {
   uint64_t* key = d.wo_key;
   uint32_t* idx = d.wo_idx;
   for (int64_t k = threadIdx.x; k < P2; k += blockDim.x) {
-    key[k] = k < n ? wo_sort_key(d.wo[k]) : ~0ull;
+    key[k] = k >= n ? ~0ull : sh ? wo_rec_key(all[1 + k]) : wo_sort_key(d.wo[k]);
     idx[k] = (uint32_t)k;
   }
   __syncthreads();
@@ -2942,10 +3009,11 @@ __global__ __launch_bounds__(1024) void K_woprep(Dev d) {
     int32_t j = 0;
     for (int32_t e = P.beg; e < P.end; ++e) {
       d.wo_erun[e] = j;  // RIGHT strings before it: its run (a RIGHT string closes run j)
-      const WoEv ev = d.wo[idx[e]];
-      const int32_t L = wo_len(d, ev);
+      int32_t L, type;
+      if (sh) { const WoRec rc = all[1 + idx[e]]; L = rc.len; type = rc.type; }
+      else { const WoEv ev = d.wo[idx[e]]; L = wo_len(d, ev); type = ev.type; }
       WoRun& R = d.wo_run[run0 + j];
-      if (ev.type == kWoDown) { R.R = L; ++j; }
+      if (type == kWoDown) { R.R = L; ++j; }
       else if (L > R.M) R.M = L;
     }
   }
@@ -2969,13 +3037,14 @@ __device__ void wo_cover_read(const Dev& d, int np, int64_t r) {
   const uint8_t* ref = d.ref + d.ref_off[s];
   auto hit = [&](int p, int code) {
     const WoPos P = d.wo_pos[p];
-    int lo = P.beg, hi = P.end;  // the position's first string from a read >= r
+    int lo = P.beg, hi = P.end;  // the position's first string from a read >= r (keys: global reads)
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (wo_key_read(d.wo_key[mid]) < r) lo = mid + 1; else hi = mid;
+      if (wo_key_read(d.wo_key[mid]) < d.read_offset + r) lo = mid + 1; else hi = mid;
     }
     const int32_t j = lo < P.end ? d.wo_erun[lo] : P.nrun - 1;
     atomicAdd(&d.wo_run[P.run0 + j].C[code], 1u);
+    if (d.wo_x) wo_cov(d)[P.run0 + j] = 1;  // (exchange: MAX; C itself stays this shard's)
   };
   // the tokenizer of :306-320: an operator applies to the operand gathered
   // after it when the next operator comes with a non-empty operand, the last
@@ -3025,6 +3094,22 @@ __device__ void wo_cover_read(const Dev& d, int np, int64_t r) {
     op = c;
     o0 = x + 1;
     olen = 0;
+  }
+}
+
+// n_shards > 1, before K_layout<true>: the cover flags reduced over the shards
+// (MAX) enter the replay as what they stand for, a LEFT string of length 1 in
+// the run.  K_layout<true> takes m = max(M, c1) with c1 from this shard's C;
+// with M >= 1 wherever ANY shard has a one-base write, m is the same on every
+// shard, and K_layout itself stays the kernel of the one-shard plan.  (M is
+// rebuilt by K_woprep every step; nothing after the layout reads it.)
+__global__ __launch_bounds__(256) void K_wofold(Dev d) {
+  const int np = (int)d.status[MPC_ST_WRAP_POS];
+  const int32_t* cov = wo_cov(d);
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < np; p += (int64_t)gridDim.x * blockDim.x) {
+    const WoPos P = d.wo_pos[p];
+    for (int32_t j = 0; j < P.nrun; ++j)
+      if (cov[P.run0 + j] != 0 && d.wo_run[P.run0 + j].M < 1) d.wo_run[P.run0 + j].M = 1;
   }
 }
 
@@ -3534,7 +3619,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
 __global__ __launch_bounds__(256) void K_worows(Dev d) {
   const int np = (int)d.status[MPC_ST_WRAP_POS];
   if (np == 0 || (d.status[MPC_ST_FLAGS] & DE_CAP)) return;
-  const int64_t n_ev = min<int64_t>((int64_t)d.status[MPC_ST_WRAP_EVENTS], d.wo_cap);
+  const int64_t n_ev = wo_listed(d);
   const int l = lane();
   const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
   const int64_t gw = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -3551,7 +3636,13 @@ __global__ __launch_bounds__(256) void K_worows(Dev d) {
   uint32_t err = 0;
   int64_t eread = INT64_MAX;
   for (int64_t e = gw; e < n_ev; e += nwaves) {
-    const WoEv ev = d.wo[d.wo_idx[e]];
+    int64_t own = d.wo_idx[e];
+    if (d.wo_x) {  // only this shard's strings: their bytes are here, at the local index
+      const WoRec rc = wo_all(d)[1 + own];
+      if (rc.shard != d.shard) continue;
+      own = rc.ev;
+    }
+    const WoEv ev = d.wo[own];
     const WoPos P = d.wo_pos[wo_lower(d.wo_pos, np, ev.g)];
     const WoRun R = d.wo_run[P.run0 + d.wo_erun[e]];
     const int64_t L = wo_len(d, ev);
@@ -3836,7 +3927,7 @@ struct mpc_plan {
     B_DIFF, B_SUB, B_MAXR, B_M, B_RUNR, B_HIR, B_LOR, B_LOF, B_ROWCNT, B_ROWBASE, B_BSUM, B_ROWS,
     B_META, B_RES, B_KEEP, B_KSUM, B_CALLS, B_NCALLS, B_MAXD, B_SROW, B_WPARSE, B_WBC, B_UNITS, B_RUNT,
     B_SUBEV, B_SUBCNT, B_WSUB, B_BKCUR, B_WWAVE, B_SUBSLAB, B_WSUBSUM, B_GCNT, B_KSLOT, B_RSFLAG, B_PGLIST,
-    B_WOEV, B_WOKEY, B_WOIDX, B_WOERUN, B_WOPOS, B_WORUN, B_COUNT
+    B_WOEV, B_WOKEY, B_WOIDX, B_WOERUN, B_WOPOS, B_WORUN, B_WOREC, B_WOALL, B_WOCOV, B_COUNT
   };
   size_t off[B_COUNT];
   size_t sz[B_COUNT];
@@ -3881,7 +3972,8 @@ Dev mpc_plan::dev() const {
   d.srow = at<int32_t>(this, B_SROW);
   d.wo = at<WoEv>(this, B_WOEV); d.wo_key = at<uint64_t>(this, B_WOKEY); d.wo_idx = at<uint32_t>(this, B_WOIDX);
   d.wo_erun = at<int32_t>(this, B_WOERUN); d.wo_pos = at<WoPos>(this, B_WOPOS); d.wo_run = at<WoRun>(this, B_WORUN);
-  d.wo_cap = wo_cap; d.wo_p2 = wo_p2;
+  d.wo_cap = wo_cap;
+  if (n_shards > 1 && wo_cap > 0) d.wo_x = at<uint8_t>(this, B_WOREC);  // (B_WOALL, B_WOCOV follow: wo_all(), wo_cov())
   return d;
 }
 
@@ -4133,7 +4225,9 @@ int mpc_plan_create(const mpc_input* in, int64_t row_cap, mpc_plan** out) {
   // read with a negative start plus its '+' insertions (>= 2 cs bytes each);
   // one shard only (the replay needs every string of a position)
   if (in->neg_reads < 0 || in->neg_cs_bytes < 0) { delete p; return fail(MPC_E_ARG, "negative neg_reads / neg_cs_bytes"); }
-  p->wo_cap = p->n_shards == 1 && in->neg_reads > 0 ? std::min<int64_t>(kWoCapMax, 2 * in->neg_reads + in->neg_cs_bytes / 2 + 16) : 0;
+  // (several shards: neg_reads / neg_cs_bytes are the totals over all of them, so every shard
+  // sizes the same list and holds all shards' strings after the gather)
+  p->wo_cap = in->neg_reads > 0 ? std::min<int64_t>(kWoCapMax, 2 * in->neg_reads + in->neg_cs_bytes / 2 + 16) : 0;
   while (p->wo_p2 < p->wo_cap) p->wo_p2 <<= 1;
   int eb = 1;
   while ((1ll << eb) <= p->G + 1) ++eb;
@@ -4429,11 +4523,21 @@ int mpc_plan_create(const mpc_input* in, int64_t row_cap, mpc_plan** out) {
   set(mpc_plan::B_WOERUN, 2 * p->wo_cap, 4);  // run of every sorted string, then K_woprep's scratch
   set(mpc_plan::B_WOPOS, p->wo_cap, sizeof(WoPos));
   set(mpc_plan::B_WORUN, p->wo_cap ? 2 * p->wo_cap + 1 : 0, sizeof(WoRun));
+  const int64_t wo_x = p->n_shards > 1 ? p->wo_cap : 0;  // the exchange buffers (counts in int32 words but WOCOV)
+  set(mpc_plan::B_WOREC, wo_x * 6, 4);
+  set(mpc_plan::B_WOALL, wo_x ? (wo_x + 1) * 6 : 0, 4);
+  set(mpc_plan::B_WOCOV, wo_x ? 2 * wo_x + 1 : 0, 4);
   size_t o = 0;
   for (int b = 0; b < mpc_plan::B_COUNT; ++b) {
     o = (o + 255) & ~(size_t)255;
     p->off[b] = o;
     o += p->sz[b];
+  }
+  // the device side finds the three exchange buffers of the wrapped odd positions from one pointer
+  if (p->off[mpc_plan::B_WOALL] != p->off[mpc_plan::B_WOREC] + (size_t)wo_a256((int64_t)p->sz[mpc_plan::B_WOREC]) ||
+      p->off[mpc_plan::B_WOCOV] != p->off[mpc_plan::B_WOALL] + (size_t)wo_a256((int64_t)p->sz[mpc_plan::B_WOALL])) {
+    delete p;
+    return fail(MPC_E_STATE, "exchange buffers of the wrapped odd positions are not adjacent");
   }
   p->ws_bytes = (o + 255) & ~(size_t)255;
   p->in.h_cs_off = nullptr;  // host array only read while planning
@@ -4532,6 +4636,9 @@ int mpc_plan_buffer(const mpc_plan* p, int which, size_t* off, int64_t* count) {
     case MPC_BUF_RUN_R: b = mpc_plan::B_RUNR; break;
     case MPC_BUF_DIFF: b = mpc_plan::B_DIFF; break;
     case MPC_BUF_SUB: b = mpc_plan::B_SUB; break;
+    case MPC_BUF_WRAP_REC: b = mpc_plan::B_WOREC; break;
+    case MPC_BUF_WRAP_ALL: b = mpc_plan::B_WOALL; break;
+    case MPC_BUF_WRAP_COVER: b = mpc_plan::B_WOCOV; break;
     default: return fail(MPC_E_ARG, "unknown buffer");
   }
   *off = p->off[b];
@@ -4597,6 +4704,8 @@ int mpc_parse(mpc_plan* p, void* stream) {
     launch_parse(p, d, st);
     launch_subs(p, d, st);
   }
+  if (d.wo_x)  // several shards, negative starts: the strings as exchange records
+    hipLaunchKernelGGL(K_wopack, dim3(std::min<unsigned>(nblk(p->wo_cap, 256), 64)), dim3(256), 0, st, d);
   HIPCHK(hipGetLastError());
   return MPC_OK;
 }
@@ -4638,13 +4747,29 @@ int mpc_tally(mpc_plan* p, void* stream) {
   return MPC_OK;
 }
 
+// the wrapped odd positions of a plan with negative starts: their runs, the
+// one-base writes of this shard's reads
+static void launch_wrap(const mpc_plan* p, const Dev& d, hipStream_t st) {
+  hipLaunchKernelGGL(K_woprep, dim3(1), dim3(1024), 0, st, d);
+  if (p->N > 0) hipLaunchKernelGGL(K_wocover, dim3(nblk(p->N, 256)), dim3(256), 0, st, d);
+}
+
+int mpc_wrap(mpc_plan* p, void* stream) {
+  NEED_BOUND(p);
+  hipStream_t st = (hipStream_t)stream;
+  Dev d = p->dev();
+  if (p->n_shards > 1 && p->wo_cap > 0) launch_wrap(p, d, st);  // (one shard: mpc_layout launches them)
+  HIPCHK(hipGetLastError());
+  return MPC_OK;
+}
+
 int mpc_layout(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
   Dev d = p->dev();
   if (p->wo_cap > 0) {  // negative starts: the wrapped odd positions first
-    hipLaunchKernelGGL(K_woprep, dim3(1), dim3(1024), 0, st, d);
-    if (p->N > 0) hipLaunchKernelGGL(K_wocover, dim3(nblk(p->N, 256)), dim3(256), 0, st, d);
+    if (p->n_shards == 1) launch_wrap(p, d, st);
+    else hipLaunchKernelGGL(K_wofold, dim3(std::min<unsigned>(nblk(p->wo_cap, 256), 64)), dim3(256), 0, st, d);
     hipLaunchKernelGGL(K_layout<true>, dim3(nblk(p->G, kGB)), dim3(kGB), 0, st, d, next_epoch());
   } else {
     hipLaunchKernelGGL(K_layout<false>, dim3(nblk(p->G, kGB)), dim3(kGB), 0, st, d, next_epoch());

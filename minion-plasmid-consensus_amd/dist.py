@@ -27,8 +27,26 @@ they are linear, so they reach the result through the rows SUM.  Layout and
 consensus are then identical on every shard.  The protocol
 is written once against an ``Exchange``: ``DistExchange`` is one shard per
 process over torch.distributed (RCCL over xGMI on GPUs; gloo in the CPU
-tests), ``LocalExchange`` drives several shards in one process (used by the
-GPU parity test to check the sharded kernels bit-exactly against one GPU).
+tests), ``LocalExchange`` drives several shards in one process (the CLI's
+``--gpus N`` through ``pileup_sharded``, and the GPU parity tests that check
+the sharded kernels bit-exactly against one GPU).
+
+A batch with negative target starts (any shard: the plans are sized from the
+totals, so every shard knows) performs six collectives.  Python's negative
+wrap writes strings into odd positions, and such a position is replayed like a
+gap over ALL reads' strings in global read order (mpc.h):
+
+    after parse     GATHER  each shard's strings as records (position, global
+                            read, length, kind, owner, owner's index): only the
+                            records present move, their counts are read on the
+                            host once per batch and cached like ``used``
+    after wrap      MAX     per run of those positions: some shard's read has a
+                            one-base write in it (the counts stay per shard and
+                            reach the result through the rows SUM)
+
+``wrap`` is the phase between tally and layout in which every shard sorts the
+gathered records -- the same positions, runs and longest strings everywhere --
+and counts its own reads' one-base writes into the runs.
 """
 import numpy as np
 
@@ -58,6 +76,15 @@ class LocalExchange:
         import torch
         for o in outs:
             o.copy_(torch.cat([t.to(o.device) for t in ts]))
+
+    def gatherv(self, ts, outs, counts, width):
+        """outs[i][: sum(counts) * width] <- the first counts[k] * width
+        elements of every ts[k], in shard order."""
+        for o in outs:
+            at = 0
+            for t, c in zip(ts, counts):
+                o[at: at + c * width].copy_(t[: c * width])
+                at += c * width
 
     def max_int(self, xs):
         return [max(xs)] * len(xs)
@@ -125,6 +152,20 @@ class DistExchange:
             return
         self._gather_rows(t, o.view(self.world, -1))
 
+    def gatherv(self, ts, outs, counts, width):
+        """Parts of unequal length (``counts`` of all ranks, known on the host):
+        one all-gather of the longest part's size, then every rank's valid
+        head copied behind the previous one.  The bytes moved follow the
+        counts, not the buffers' capacity."""
+        (t,), (o,) = ts, outs
+        m = max(1, max(counts)) * width
+        send = t[:m]
+        rows = self._gather_rows(send.cpu() if self.host_staged and send.is_cuda else send)
+        at = 0
+        for k, c in enumerate(counts):
+            o[at: at + c * width].copy_(rows[k, : c * width])
+            at += c * width
+
     def _ints(self, xs, op):
         import torch
         dev = "cuda" if self.dist.get_backend(self.group) == "nccl" else "cpu"
@@ -169,14 +210,50 @@ def shard_layout(n_reads_per_shard):
     return [int(o) for o in offs[:-1]], int(offs[-1])
 
 
-def exchange_step(plans, ex, mdf, gtf, stream=None, used=None):
+def wrap_counts(plans, ex):
+    """Records every shard (all shards, in shard order) sends of its strings
+    in wrapped odd positions.  Reads the local counts on the host (after the
+    parse) and, over a process group, exchanges them: once per batch."""
+    import torch
+    cap = plans[0].buffer(eng.BUF_WRAP_REC, torch.int32).numel() // eng.WRAP_REC_WORDS
+    local = [min(int(p.buffer(eng.BUF_STATUS, torch.int32)[eng.MPC_ST_WRAP_EVENTS].item()) & 0xFFFFFFFF, cap)
+             for p in plans]
+    return ex.sizes(local)
+
+
+def _wrap_gather(plans, ex, counts):
+    """Collective A: every shard's valid records, in shard order, behind the
+    header record that tells K_woprep how many they are.  Returns the gathered
+    record count."""
+    import torch
+    i32, W = torch.int32, eng.WRAP_REC_WORDS
+    cap = plans[0].buffer(eng.BUF_WRAP_REC, i32).numel() // W
+    keep, room = [], cap  # (past the list bound: dropped; the header's true total flags DE_UNSUPPORTED)
+    for c in counts:
+        keep.append(min(c, room))
+        room -= keep[-1]
+    ex.gatherv([p.buffer(eng.BUF_WRAP_REC, i32) for p in plans],
+               [p.buffer(eng.BUF_WRAP_ALL, i32)[W:] for p in plans], keep, W)
+    for p in plans:
+        head = p.buffer(eng.BUF_WRAP_ALL, i32)[:W]
+        head.zero_()
+        head[:1].fill_(min(sum(counts), 2 ** 31 - 1))
+    return sum(keep)
+
+
+def exchange_step(plans, ex, mdf, gtf, stream=None, used=None, cache=None):
     """One global pileup over the shards in ``plans`` (all of this process's
     shards; with DistExchange exactly one).  Collective: every shard must call it.
     ``used`` (the runs in use, see below) is a property of the shards' reads:
     a caller that steps the same batches again passes the value this function
-    returned for them, and the step then has no host synchronisation."""
+    returned for them, and the step then has no host synchronisation.  The
+    same holds for the record counts of a batch with negative starts: they are
+    kept in ``cache`` (a dict the caller owns, one per set of batches)."""
     import torch
     i32 = torch.int32
+    # negative starts anywhere in the batch (a plan attribute, the same on every
+    # shard: the plans were sized from the totals): two more collectives
+    wrap = bool(getattr(plans[0], "wrap", False))
 
     def each(phase, *args):
         for p in plans:
@@ -184,6 +261,13 @@ def exchange_step(plans, ex, mdf, gtf, stream=None, used=None):
 
     each("parse")
     ex.reduce([p.buffer(eng.BUF_HASLEFT, i32) for p in plans], "or")
+    if wrap:
+        counts = cache.get("wrap") if cache is not None else None
+        if counts is None:
+            counts = wrap_counts(plans, ex)
+            if cache is not None:
+                cache["wrap"] = counts
+        n_wrap = _wrap_gather(plans, ex, counts)
     each("index")
     ex.gather([p.buffer(eng.BUF_RIGHT_CNT, i32) for p in plans], [p.buffer(eng.BUF_RIGHT_CNT_ALL, i32) for p in plans])
     each("runs")
@@ -216,6 +300,13 @@ def exchange_step(plans, ex, mdf, gtf, stream=None, used=None):
         ex.reduce(tails, "max")
     for src, dst in parked:
         dst.copy_(src)
+    if wrap:
+        # the runs of the wrapped odd positions over all shards' strings, each
+        # shard's one-base writes counted into them; whether ANY shard has one
+        # in a run decides the layout (the counts themselves reach the result
+        # through the rows SUM).  Runs <= 2 x the gathered strings.
+        each("wrap")
+        ex.reduce([p.buffer(eng.BUF_WRAP_COVER, i32)[: 2 * n_wrap + 1] for p in plans], "max")
     each("layout")
     each("rows")
     ex.reduce([p.buffer(eng.BUF_ROWS, i32) for p in plans], "sum")
@@ -247,6 +338,16 @@ class ShardedPileup:
         offs, ng = shard_layout(n_all)
         self.batches = [eng.Batch(smp, device=dev, read_offset=offs[r], n_reads_global=ng, shard=r,
                                   n_shards=n_shards, parse_cus=parse_cus) for smp, dev, r in zip(shards, devices, ranks)]
+        # negative starts: every shard sizes its plan from the totals over all
+        # shards (mpc.h neg_reads), so all of them plan the same kernels and
+        # the same collectives, also those holding no negative start
+        neg = sum(self.ex.sizes([b.neg_reads for b in self.batches]))
+        neg_cs = sum(self.ex.sizes([b.neg_cs_bytes for b in self.batches]))
+        for b in self.batches:
+            b.neg_reads, b.neg_cs_bytes = neg, neg_cs
+        # reads of every sample on every local shard: maps a shard's read index
+        # back to the launch order of one GPU (data_error)
+        self._counts = [[len(s["tstart"]) for s in smp] for smp in shards]
         cap = row_cap or max(b.row_estimate() for b in self.batches)
         cap = self.ex.max_int([cap] * local)[0] if isinstance(self.ex, DistExchange) else cap
         self.plans = [eng.Plan(b, cap) for b in self.batches]
@@ -255,11 +356,13 @@ class ShardedPileup:
         # batches are fixed for the object's lifetime (mpc_plan_set_input is
         # never called on them); rebind() resets it
         self._used = None
+        self._cache = {}  # record counts of the wrapped odd positions, cached like _used
 
     def rebind(self):
-        """Forget the cached run count (call after changing any shard's inputs
-        in place): the next step re-reads it before the run-array MAX."""
+        """Forget the cached counts (call after changing any shard's inputs
+        in place): the next step re-reads them."""
         self._used = None
+        self._cache = {}
         self._sized = False
 
     # bench.py interface (one local shard)
@@ -274,7 +377,7 @@ class ShardedPileup:
     def step(self, mdf, gtf, stream=None):
         # the runs in use depend only on the reads: read back once, reused by
         # later steps over the same batches (no host sync inside a step)
-        used = exchange_step(self.plans, self.ex, mdf, gtf, stream, self._used)
+        used = exchange_step(self.plans, self.ex, mdf, gtf, stream, self._used, self._cache)
         if not self._sized:
             # the layout (and so the row count) is identical on every shard
             st = self.plans[0].status()
@@ -283,7 +386,7 @@ class ShardedPileup:
             if flags & eng.DE_CAPACITY:
                 need = int(st[eng.MPC_ST_ROWS_NEEDED]) + 16
                 self.plans = [eng.Plan(b, need) for b in self.batches]
-                used = exchange_step(self.plans, self.ex, mdf, gtf, stream)
+                used = exchange_step(self.plans, self.ex, mdf, gtf, stream, None, self._cache)
             self._sized = True
             self._used = used
 
@@ -293,5 +396,66 @@ class ShardedPileup:
             if int(st[eng.MPC_ST_FLAGS]):
                 raise eng.DataError(int(st[eng.MPC_ST_FLAGS]), int(st[eng.MPC_ST_FIRST_READ]))
 
+    def data_error(self):
+        """(OR of all local shards' MPC_DE_* flags, read index) -- the index
+        one GPU would report for the same samples: every shard's first
+        offending read mapped back through the contiguous split to the launch
+        order (sample by sample, reads in order), the smallest of them; None
+        when no shard names a read.  (0, None): no error."""
+        flags, first = 0, None
+        totals = [sum(c[s] for c in self._counts) for s in range(len(self._counts[0]))]
+        for k, p in enumerate(self.plans):
+            st = p.status()
+            flags |= int(st[eng.MPC_ST_FLAGS])
+            r = int(st[eng.MPC_ST_FIRST_READ])
+            if not int(st[eng.MPC_ST_FLAGS]) or r == 0xFFFFFFFF:
+                continue
+            for s, c in enumerate(self._counts[k]):
+                if r < c or s == len(totals) - 1:
+                    break
+                r -= c
+            g = sum(totals[:s]) + sum(self._counts[j][s] for j in range(k)) + r
+            first = g if first is None else min(first, g)
+        return flags, first
+
     def fetch(self):
         return self.plans[0].fetch()
+
+
+def shard_count(n_devices, n_reads):
+    """Shards a group of ``n_reads`` reads is split into over ``n_devices``."""
+    return max(1, min(int(n_devices), int(n_reads)))
+
+
+def assign(n_groups, n_gpus, device=0, visible=1):
+    """How ``--gpus N`` spreads job groups: a pure function of its arguments.
+    The devices are ``device + k`` (k < N) modulo the visible ones.  With at
+    least N groups, group i goes to worker ``i % N`` (one device each, no
+    collective): returns ("partition", devices, worker of every group).
+    With fewer, every group is read-sharded over all N devices:
+    ("shard", devices, None)."""
+    n, visible = max(1, int(n_gpus)), max(1, int(visible))
+    devices = [(int(device) + k) % visible for k in range(n)]
+    if n_groups >= n:
+        return "partition", devices, [i % n for i in range(n_groups)]
+    return "shard", devices, None
+
+
+def pileup_sharded(samples, mdf, gtf, devices):
+    """engine.pileup over the reads split into contiguous shards, one per
+    entry of ``devices`` (entries may repeat: several shards on one device),
+    at most one shard per read.  Same result, same DataError (flags of all
+    shards, the read index in the launch order of one GPU)."""
+    import torch
+    k = shard_count(len(devices), sum(len(s["tstart"]) for s in samples))
+    if k == 1:
+        return eng.pileup(samples, mdf, gtf, devices[0])
+    sp = ShardedPileup(split_samples(samples, k), list(devices[:k]))
+    sp.step(mdf, gtf)
+    flags, first = sp.data_error()
+    if flags:
+        raise eng.DataError(flags, 0xFFFFFFFF if first is None else first)
+    res = sp.fetch()
+    for d in set(devices[:k]):
+        torch.cuda.synchronize(d)
+    return res

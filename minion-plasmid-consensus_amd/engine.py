@@ -20,8 +20,10 @@ MPC_ST_FLAGS, MPC_ST_FIRST_READ, MPC_ST_ROWS_NEEDED, MPC_ST_MIXED, MPC_ST_RSORT_
 MPC_ST_WRAP_EVENTS, MPC_ST_WRAP_POS = 6, 7
 DE_OP, DE_VALUE, DE_INDEX, DE_KEY, DE_CAPACITY, DE_INTERNAL, DE_UNSUPPORTED = 1, 2, 4, 8, 16, 32, 64
 (BUF_STATUS, BUF_CALLS, BUF_NCALLS, BUF_MAXDEPTH, BUF_ROWS, BUF_ROWMETA, BUF_RIGHT_CNT, BUF_RIGHT_CNT_ALL,
- BUF_HASLEFT, BUF_MAXR, BUF_RUN_M, BUF_RUN_R, BUF_DIFF, BUF_SUB) = range(14)
-PHASES = ("parse", "index", "runs", "tally", "layout", "rows")
+ BUF_HASLEFT, BUF_MAXR, BUF_RUN_M, BUF_RUN_R, BUF_DIFF, BUF_SUB, BUF_WRAP_REC, BUF_WRAP_ALL,
+ BUF_WRAP_COVER) = range(17)
+WRAP_REC_WORDS = 6  # int32 words of one exchanged record (mpc.h MPC_BUF_WRAP_REC)
+PHASES = ("parse", "index", "runs", "tally", "wrap", "layout", "rows")
 
 DE_NAMES = {DE_OP: "Unknown operator", DE_VALUE: "ValueError", DE_INDEX: "IndexError", DE_KEY: "KeyError",
             DE_CAPACITY: "row capacity", DE_INTERNAL: "internal invariant",
@@ -348,6 +350,8 @@ class Batch:
         neg = tstart < 0
         self.neg_reads = int(neg.sum())
         self.neg_cs_bytes = int((cs_off[1:] - cs_off[:-1])[neg].sum()) if self.neg_reads else 0
+        # (a shard of several: dist.ShardedPileup replaces both by the totals over
+        # all shards before it plans, mpc.h)
         self.aligned_bases = int(sum(int(np.asarray(s.get("aligned", [0])).sum()) for s in samples))
 
         def dev(a, pad=0):
@@ -418,6 +422,9 @@ class Plan:
         self.ws = self.ws_raw[pad: pad + self.ws_bytes]
         self._views = {}
         _check(L.mpc_plan_bind(h, ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes))
+        # a shard of a batch with negative starts: the exchange adds the two
+        # collectives of the wrapped odd positions (dist.exchange_step)
+        self.wrap = batch.n_shards > 1 and batch.neg_reads > 0
 
     def __del__(self):
         h = getattr(self, "h", None)

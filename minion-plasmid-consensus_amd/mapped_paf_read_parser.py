@@ -6,6 +6,11 @@ to point ``params.script`` here.
 
 Extra, optional flags (defaults keep the reference behaviour):
   --device N         HIP device index (default 0)
+  --gpus N           use N GPUs (default 1), devices --device .. --device + N - 1
+                     modulo the visible ones.  Jobs with their own reads files
+                     (--job) are dealt round-robin to the GPUs; with fewer reads
+                     files than GPUs every pileup is read-sharded over all N
+                     (dist.py).  Same files, same exit status as with one GPU.
   --also REF PAF CONSENSUS CHROMAT ACCURACIES
                      run another (assembly, PAF) pair against the same --reads in
                      the SAME launch (e.g. the antisense strand); repeatable
@@ -53,6 +58,8 @@ def build_parser():
     p.add_argument("-d", "--debug", action="store_true", dest="DEBUG", help="Flag for setting debug/test state.")
     p.add_argument("-v", "--verbose", action="store_true", dest="VERB", help="Flag for setting verbose output.")
     p.add_argument("--device", type=int, default=0, help="HIP device index")
+    p.add_argument("--gpus", type=int, default=1,
+                   help="GPUs to use: job groups dealt round-robin, or read-sharded when there are fewer groups")
     p.add_argument("--also", nargs=5, action="append", default=[],
                    metavar=("REF", "PAF", "CONSENSUS", "CHROMAT", "ACCURACIES"),
                    help="additional (assembly, PAF) job against the same reads, same launch")
@@ -73,14 +80,32 @@ def _ingest_and_pileup(ingest, engine, jobs, args, tm):
     Returns the per-job call dicts, or None when --min_depth_factor is missing
     (every file is still read first, as the reference does).  ``tm`` receives
     the phase walls: ingest (all groups), device (what the ingest did not
-    hide)."""
+    hide).
+
+    ``--gpus N`` (dist.assign): with at least N groups, group i runs whole on
+    the worker thread of device i % N; with fewer, every group is read-sharded
+    over all N devices by one worker (dist.pileup_sharded).  The results, the
+    error a run reports and their order are those of one GPU."""
     import concurrent.futures as cf
+    import contextlib
     mdf, gtf = args.MIN_DEPTH_FACTOR, args.GLOBAL_THRESHOLD_FACTOR
     triples = [(ref, paf, reads) for ref, paf, reads, *_ in jobs]
     groups = ingest.job_groups(triples)
     packed, futs, t_ing = [None] * len(jobs), [], 0.0
-    with cf.ThreadPoolExecutor(max_workers=1) as dev:
-        for idx in groups:
+    mode, devices, worker_of = "partition", [args.device], [0] * len(groups)
+    if args.gpus > 1:
+        import torch
+        dist = importlib.import_module(engine.__name__.rsplit(".", 1)[0] + ".dist")
+        engine.lib()  # (loaded once, before the workers race for it)
+        visible = torch.cuda.device_count()
+        if args.gpus > visible:
+            statprint("--gpus {} with {} visible: several shards or partitions share a device.".format(
+                args.gpus, visible), "WARNING")
+        mode, devices, worker_of = dist.assign(len(groups), args.gpus, args.device, visible)
+    with contextlib.ExitStack() as stack:
+        pools = [stack.enter_context(cf.ThreadPoolExecutor(max_workers=1))
+                 for _ in range(len(devices) if mode == "partition" else 1)]
+        for gi, idx in enumerate(groups):
             t = time.perf_counter()
             got = ingest.pack_group([triples[j] for j in idx])
             t_ing += time.perf_counter() - t
@@ -92,8 +117,13 @@ def _ingest_and_pileup(ingest, engine, jobs, args, tm):
                     statprint("There were {} mapped reads.".format(x["n_alignments"]))
             if ok and mdf is not None:
                 if not futs:
-                    statprint("Pileup and consensus on device {}...".format(args.device))
-                futs.append((idx, dev.submit(engine.pileup, got, mdf, 1.0 if gtf is None else gtf, args.device)))
+                    statprint("Pileup and consensus on device {}...".format(",".join(str(d) for d in devices)))
+                if mode == "partition":
+                    w = worker_of[gi]
+                    fut = pools[w].submit(engine.pileup, got, mdf, 1.0 if gtf is None else gtf, devices[w])
+                else:
+                    fut = pools[0].submit(dist.pileup_sharded, got, mdf, 1.0 if gtf is None else gtf, devices)
+                futs.append((idx, fut))
         t1 = time.perf_counter()
         tm["ingest"] = t_ing
         errs = [x for x in packed if isinstance(x, Exception)]
@@ -136,7 +166,10 @@ def main(argv=None, timings=None):
     """CLI entry.  ``timings`` (a dict, optional) receives the wall seconds of
     the phases: ingest, device (H2D + kernels + D2H), write."""
     t_main = time.perf_counter()
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.gpus < 1:
+        parser.error("--gpus must be at least 1")
     tm = timings if timings is not None else {}
     pkg = _pkg()
     ingest, engine, writers = pkg.ingest, pkg.engine, pkg.writers
