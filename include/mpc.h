@@ -60,10 +60,11 @@ extern "C" {
 #define MPC_DE_CAPACITY 16u /* row capacity too small: re-plan with status[MPC_ST_ROWS_NEEDED] */
 #define MPC_DE_INTERNAL 32u /* invariant violated (bug) */
 #define MPC_DE_UNSUPPORTED 64u /* input the reference accepts but this engine does not: a ':' / '-' advance
-                                  of 2^22 or more from a negative coordinate; tstart < MPC_TSTART_MIN; a
-                                  write into a wrapped ODD position (below) in a plan that declared no
-                                  negative starts (mpc_input.neg_reads = 0; with n_shards > 1: no shard
-                                  declared one), or more such strings than the list bound (2^22) */
+                                  of 2^22 or more from a negative coordinate; tstart < MPC_TSTART_MIN; ANY
+                                  tstart < 0 -- not only one whose read writes into a wrapped ODD position
+                                  (below) -- in a plan that declared no negative starts (mpc_input.neg_reads
+                                  = 0; with n_shards > 1: no shard declared one); more strings in wrapped
+                                  odd positions than the list bound (2^22) */
 
 /* Lowest target start the engine takes.  Negative starts (minimap2 never
  * writes one) follow the reference's Python negative indexing (:222,
@@ -141,7 +142,9 @@ typedef struct {
   /* reads with tstart < 0 and their cs bytes (host counts; 0, 0 when there
    * are none).  They bound the strings Python's negative wrap writes into odd
    * positions (upstream / downstream flanks, '+' insertions at i in [-n, 0));
-   * a plan sized with 0 reports such a write as MPC_DE_UNSUPPORTED.  With
+   * any tstart < 0 requires neg_reads > 0: a plan sized with 0 compiles none
+   * of the negative-coordinate rounds and reports every read with tstart < 0
+   * as MPC_DE_UNSUPPORTED, also one that writes nothing there (matches only).  With
    * n_shards > 1 both are the TOTALS over all shards, the same on every shard:
    * every shard then plans the same K_parse, list capacity and layout kernel,
    * and the two extra collectives line up on shards without a negative start. */

@@ -92,10 +92,11 @@ __device__ __forceinline__ int uniform_i32(int x) { return __builtin_amdgcn_read
 
 __device__ __forceinline__ uint64_t ballot(bool p) { return (uint64_t)__ballot(p ? 1 : 0); }
 
-// Python str.strip() whitespace restricted to ASCII (the only bytes that can
-// appear inside a tab-separated, rstrip()ed PAF field).
+// Whitespace int() strips from an ASCII str: space and \t \n \v \f \r.  NOT
+// the separators 0x1c-0x1f, which str.strip() removes but int() rejects in an
+// ASCII operand (ValueError; golden n_neg_pyint_fs).
 __device__ __forceinline__ bool py_space(uint32_t c) {
-  return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == 0x0b || c == 0x0c || (c >= 0x1c && c <= 0x1f);
+  return c == ' ' || (c >= 0x09 && c <= 0x0d);
 }
 
 // int(operand) of processOperation ':' (:77) in base 10 on ASCII bytes:

@@ -570,7 +570,14 @@ __device__ __noinline__ TokInfo analyze_long(const uint8_t* cs, int64_t s, int64
   } else if (op == '+') {
     if (olen == 0) return r;
     bool ok = true;
-    for (int64_t x = s + 1; x < e; ++x) ok &= code_upper(cs[x]) >= 0;
+    for (int64_t x = s + 1; x < e; ++x) {
+      const int cd = code_upper(cs[x]);
+      ok &= cd >= 0;
+      // an inline insertion (<= kInsInline bases) travels with its bases in the
+      // event word, base k at bits 2k (the window decode's pk): a short '+'
+      // gets here behind a ':' prefix that is not plain digits (": 12+ac")
+      if (x - s - 1 < kInsInline) r.pay |= (uint32_t)(cd & 3) << (2 * (x - s - 1));
+    }
     if (!ok) r.err |= DE_KEY;
     r.kind = 3;
   } else if (op == '-') {
@@ -3059,14 +3066,13 @@ __device__ void wo_cover_read(const Dev& d, int np, int64_t r) {
     if (!end && !sp) { ++olen; continue; }
     if (end || olen > 0) {
       if (op == ':') {
+        // int(operand) exactly as K_parse takes it (analyze_long): every form
+        // py_int accepts advances here too, or the read's later one-base
+        // writes at listed positions would be lost without any flag
         int64_t m = 0;
-        if (olen == 0) return;
-        for (int64_t y = o0; y < o0 + olen; ++y) {
-          const uint32_t dc = (uint32_t)d.cs[y] - 0x30u;
-          if (dc > 9u) return;
-          m = m * 10 + dc;
-          if (m > (1ll << 40)) m = 1ll << 40;
-        }
+        if (!py_int(d.cs + o0, olen, &m)) return;  // ValueError: K_parse flagged DE_VALUE
+        if (m < 0) m = 0;
+        if (m > (1ll << 40)) m = 1ll << 40;
         const int64_t k0 = i < 0 ? 0 : i, k1 = i + m < n ? i + m : n;
         for (int p = k0 < k1 ? wo_lower(d.wo_pos, np, gb + k0) : pb; p < pb && d.wo_pos[p].g < gb + k1; ++p) {
           const int code = base_code_exact(ref[d.wo_pos[p].g - gb]);

@@ -120,9 +120,10 @@ static int right_indel(Pos* obs, int64_t P, int64_t x0, const char* str, int64_t
   return 0;
 }
 
+/* what int() strips from an ASCII str: not 0x1c-0x1f (str.strip() removes those,
+ * int() raises ValueError on them; golden n_neg_pyint_fs) */
 static int is_pyspace(char c) {
-  return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\x0b' || c == '\x0c' ||
-         (c >= '\x1c' && c <= '\x1f');
+  return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\x0b' || c == '\x0c';
 }
 
 /* Python int(str) in base 10 restricted to ASCII: strip, optional sign, digits with

@@ -281,6 +281,31 @@ def negative_cases(script):
               "a read ending below 0 with a downstream flank: slots appended to a wrapped odd position")
 
 
+def negative_pyint_cases(script):
+    """int() forms of a ':' operand (:77) on reads with a negative target start:
+    the coordinates they advance decide which later writes land in a wrapped
+    odd position and which reads cover it.  Position 10 of the output holds
+    the wrapped rows (odd position n - 1); three of the four reads reach it
+    only after a decorated ':'.  The plain-digit twin (':11', ':10',
+    ':2*ca:7') gives the same files."""
+    R = ">ref\nACGTACGTAC\n"
+    reads = ">r1\nACGTACGTAC\n>r2\nAAACGTACGTACG\n>r3\nACGTACGTAC\n>r4\nGGCAAGTACGTA\n"
+    r1 = paf_line("r1", 10, 0, 10, "+", 0, 10, ":10")
+    r3 = paf_line("r3", 10, 0, 10, "+", 0, 10, ": 1_0")
+
+    def case(name, cs2, cs4, note):
+        paf = r1 + paf_line("r2", 13, 0, 13, "+", -1, 10, cs2) + r3 + paf_line("r4", 12, 2, 12, "+", -1, 9, cs4)
+        assert all(not ln.endswith((" ", "\x0b", "\x0c", "\x1f")) for ln in paf.split("\n"))  # (:197 rstrip)
+        emit_case(script, name, R, reads, paf, [(0, 1), (-1, 1)], note)
+
+    case("n_neg_pyint", "+aa:1_1", ": 2*ca:0_7", "negative tstart with ' d', 'd_d' and '0_d' operands of ':'")
+    case("n_neg_pyint_ws", "+aa:\x0b5:0_6", ":2*ca:3\x0c:\x0b4",
+         "\\x0b / \\x0c around the digits of a ':' operand in the middle of the cs")
+    case("n_neg_pyint_bad", "+aa:1__1", ": 2*ca:0_7", "int('1__1') on a negative-start read -> ValueError")
+    case("n_neg_pyint_fs", "+aa:\x1f5:6", ": 2*ca:0_7",
+         "\\x1f is whitespace to str.strip() but not to int() of an ASCII str -> ValueError")
+
+
 def long_reference_cases(script):
     """A reference one base past the engine's coordinate limit (include/mpc.h:
     n <= 2^22 - 2 = 4,194,302; the reference takes any length, :161-184), with
@@ -329,8 +354,8 @@ def long_reference_cases(script):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref-script", default="/root/reference/src/mapped_paf_read_parser.py")
-    ap.add_argument("--only", default="", help="'unicode' / 'negative' / 'long': regenerate only the non-ASCII / negative-tstart / "
-                                            "past-the-length-limit cases")
+    ap.add_argument("--only", default="", help="'unicode' / 'negative' / 'neg_pyint' / 'long': regenerate only the non-ASCII / "
+                                            "negative-tstart / negative-tstart int() / past-the-length-limit cases")
     a = ap.parse_args()
     os.makedirs(GOLDEN, exist_ok=True)
     if a.only == "unicode":
@@ -339,12 +364,16 @@ def main():
     if a.only == "negative":
         negative_cases(a.ref_script)
         return
+    if a.only == "neg_pyint":
+        negative_pyint_cases(a.ref_script)
+        return
     if a.only == "long":
         long_reference_cases(a.ref_script)
         return
     hand_cases(a.ref_script)
     unicode_cases(a.ref_script)
     negative_cases(a.ref_script)
+    negative_pyint_cases(a.ref_script)
     long_reference_cases(a.ref_script)
     random_cases(a.ref_script)
 
