@@ -7,9 +7,12 @@ Modules
   writers  Step 7 output files
   synth    seeded synthetic cs-tagged data (tests / bench)
   dist     multi-GPU read sharding over RCCL (torch.distributed)
+  verify   exact alignment of consensus files with the expected plasmid (K_vscan)
   mapped_paf_read_parser  the drop-in CLI
+  verify_consensus        the "Check the results" CLI
 """
 from . import _build, ingest, writers, synth  # noqa: F401
 from . import engine  # noqa: F401
+from . import verify  # noqa: F401
 
-__all__ = ["ingest", "engine", "writers", "synth"]
+__all__ = ["ingest", "engine", "writers", "synth", "verify"]

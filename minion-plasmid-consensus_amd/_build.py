@@ -1,9 +1,10 @@
 """In-tree builds of the native libraries (no JIT cache: the .so files travel with
 the repo snapshot to the GPU box).
 
-  libmpc.so        HIP kernels + C-ABI (include/mpc.h), hipcc --offload-arch=gfx950
+  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan), hipcc --offload-arch=gfx950
   libmpc_synth.so  host-only synthetic data generator (g++)
   libmpc_ingest.so native host I/O: ingest (Steps 1-3) and writers (Step 7) (include/mpc_ingest.h, g++ -pthread)
+                   and the host half of verify_consensus (include/mpc_verify.h)
 """
 import os
 import subprocess
@@ -16,7 +17,7 @@ LIBMPC = os.path.join(PKG, "libmpc.so")
 LIBSYNTH = os.path.join(PKG, "libmpc_synth.so")
 LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 
-HIP_SOURCES = ["mpc_kernels.hip"]
+HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip"]
 HIP_HEADERS = ["mpc_device.h"]
 
 
@@ -39,9 +40,9 @@ def ensure_synth():
 
 
 def build_ingest(force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("ingest.cpp", "writers.cpp", "pseudopair.cpp")]
-    hdr = os.path.join(INCLUDE, "mpc_ingest.h")
-    if force or _stale(LIBINGEST, srcs + [hdr, os.path.join(CSRC, "host_threads.h")]):
+    srcs = [os.path.join(CSRC, f) for f in ("ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp")]
+    hdrs = [os.path.join(INCLUDE, h) for h in ("mpc_ingest.h", "mpc_verify.h")]
+    if force or _stale(LIBINGEST, srcs + hdrs + [os.path.join(CSRC, "host_threads.h")]):
         subprocess.run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I", INCLUDE, "-o", LIBINGEST] + srcs,
                        check=True)
     return LIBINGEST
@@ -51,7 +52,7 @@ def build_hip(force=False, extra=(), out=None):
     """libmpc.so (``out``/``extra``: experiment variants, e.g. -DMPC_TUNING_OVERRIDES)."""
     out = out or LIBMPC
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, "mpc.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h")]
     if force or extra or _stale(out, deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

@@ -3894,6 +3894,8 @@ static uint32_t next_epoch() {
   return v;
 }
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+// the library's other translation units (mpc_verify.hip) report through the same mpc_last_error()
+__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg) { return fail(code, msg); }
 
 #define HIPCHK(x)                                                                  \
   do {                                                                             \
