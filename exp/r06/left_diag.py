@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """K_left event paths of one single-batch step (diagnostic build exp/v/leftdiag.so):
-   KEXP_CFG=c3 python3 exp/r06/left_diag.py exp/v/leftdiag.so"""
+   KEXP_CFG=c3 python3 exp/r06/left_diag.py exp/v/leftdiag.so
+Needs the source of commit a668828, the last one with the diagnostic counters
+(-DMPC_LEFT_DIAG, mpc_diag_left): DESIGN.md section 7, dropped variants."""
 import ctypes
 import importlib
 import os

@@ -51,10 +51,8 @@
 #else
 #define MPC_BF_TUNING_ 0
 #endif
-#if defined(MPC_PARSE_DMA) || defined(MPC_FAST_DECODE_MODES) || defined(MPC_LDS_BASE_MODES) || defined(MPC_EPI_U) || \
-    defined(MPC_SUBS_SLAB) || defined(MPC_LAYOUT_GAPS) || defined(MPC_LOOKBACK_U) ||     \
-    defined(MPC_FLANK_BLOCKS_MAX) || defined(MPC_BPERM_BASE_MODES) || defined(MPC_FLANK_WAVES) || defined(MPC_CS_NT) || defined(MPC_SUB1) || defined(MPC_EARLY_PLACE) || defined(MPC_FLANK_SMALL_BELOW) || \
-    defined(MPC_PREFETCH_CS_MODES) || defined(MPC_INT_CHECK_MODES) || defined(MPC_DEFER_PLACE) || defined(MPC_DEFER_SUBEV) || defined(MPC_LEFT_INTERP) || defined(MPC_FLUSH_X2)
+#if defined(MPC_LDS_BASE_MODES) || defined(MPC_LAYOUT_GAPS) || defined(MPC_FLANK_WAVES) || \
+    defined(MPC_FLANK_BLOCKS_MAX) || defined(MPC_FLANK_SMALL_BELOW)
 #define MPC_BF_VARIANT_ 4
 #else
 #define MPC_BF_VARIANT_ 0
@@ -93,22 +91,17 @@ constexpr uint32_t kNullGap = 0x3fffffu;
 // (1 = a block's own sum, 2 = its inclusive prefix), the launch epoch in bits
 // 32-61, the 32-bit value below
 constexpr uint64_t kSelAgg = 1ull << 62, kSelPre = 2ull << 62, kSelTag = 0x3fffffffull << 32;
-// look-back predecessors per lane and step (1: 64 per step)
-#ifndef MPC_LOOKBACK_U
-#define MPC_LOOKBACK_U 1
-#endif
 
 // Decoupled look-back, called by ONE wave of block b: publishes the block's NV
 // values (own[k], flag 1), sums its predecessors' values back to the nearest
 // inclusive prefix, publishes its own inclusive prefix (flag 2) and returns the
 // exclusive prefixes in pre[k].  Block b's NV words are st[NV*b .. NV*b+NV-1]; a
 // predecessor counts once all its words carry this launch's tag and the same
-// flag.  Each step reads 64 x U predecessors (U per lane).  The launches use
-// U = 1 (MPC_LOOKBACK_U, 64 per step): U = 4 (256 per step, 11 instead of 44
-// dependent steps over C5's 2.8 k blocks) measured the same within +-4 us
-// (profiles/r03_experiments/lookback_variants.txt).  Blocks are dispatched in index order, so the blocks
-// waited on are running or done; the spin is bounded anyway (DE_INTERNAL).
-template <int NV, int U>
+// flag.  Each step reads 64 predecessors, one per lane (wider steps measured
+// the same: DESIGN.md §7, dropped variants).  Blocks are dispatched in index
+// order, so the blocks waited on are running or done; the spin is bounded
+// anyway (DE_INTERNAL).
+template <int NV>
 __device__ void lookback(uint64_t* st, int64_t b, uint64_t tag, const int32_t* own, int64_t* pre, uint32_t* flags) {
   const int l = lane();
   if (l == 0)
@@ -119,29 +112,19 @@ __device__ void lookback(uint64_t* st, int64_t b, uint64_t tag, const int32_t* o
   for (int k = 0; k < NV; ++k) acc[k] = 0;
   int spins = 0;
   for (int64_t j0 = b - 1; j0 >= 0;) {
-    uint64_t x[U][NV];
+    uint64_t x[NV];
+    const int64_t j = j0 - l;  // distance l; before block 0: prefixes of 0
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t j = j0 - 64 * u - l;  // distance 64 u + l; before block 0: prefixes of 0
+    for (int k = 0; k < NV; ++k)
+      x[k] = j >= 0 ? __hip_atomic_load(st + NV * j + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (kSelPre | tag);
+    // every predecessor up to the nearest prefix must be ready
+    bool ready = (x[0] & kSelTag) == tag && (x[0] >> 62) != 0;
 #pragma unroll
-      for (int k = 0; k < NV; ++k)
-        x[u][k] = j >= 0 ? __hip_atomic_load(st + NV * j + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (kSelPre | tag);
-    }
-    // windows u = 0.. in order of distance: every predecessor up to the nearest
-    // prefix must be ready
-    bool ok = true, found = false;
-    uint64_t need[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      bool ready = (x[u][0] & kSelTag) == tag && (x[u][0] >> 62) != 0;
-#pragma unroll
-      for (int k = 1; k < NV; ++k) ready = ready && (x[u][k] & kSelTag) == tag && (x[u][k] >> 62) == (x[u][0] >> 62);
-      const uint64_t rdy = ballot(ready), pfx = ballot(ready && (x[u][0] >> 62) == 2);
-      need[u] = found ? 0ull : (pfx ? (pfx & (0 - pfx)) * 2 - 1 : ~0ull);
-      ok = ok && (rdy & need[u]) == need[u];
-      found = found || pfx != 0;
-    }
-    if (!ok) {
+    for (int k = 1; k < NV; ++k) ready = ready && (x[k] & kSelTag) == tag && (x[k] >> 62) == (x[0] >> 62);
+    const bool is_pre = (x[0] >> 62) == 2;
+    const uint64_t rdy = ballot(ready), pfx = ballot(ready && is_pre);
+    const uint64_t need = pfx ? (pfx & (0 - pfx)) * 2 - 1 : ~0ull;
+    if ((rdy & need) != need) {
       if (++spins > (1 << 22)) {  // never expected: in-order dispatch
         if (l == 0) atomicOr(flags, (uint32_t)MPC_DE_INTERNAL);
         break;
@@ -150,14 +133,9 @@ __device__ void lookback(uint64_t* st, int64_t b, uint64_t tag, const int32_t* o
       continue;
     }
 #pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      int32_t v = 0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) v += ((need[u] >> l) & 1ull) ? (int32_t)(uint32_t)x[u][k] : 0;
-      acc[k] += wave_sum(v);
-    }
-    if (found) break;
-    j0 -= 64 * U;
+    for (int k = 0; k < NV; ++k) acc[k] += wave_sum(((need >> l) & 1ull) ? (int32_t)(uint32_t)x[k] : 0);
+    if (pfx != 0) break;
+    j0 -= 64;
   }
   if (l == 0 && b > 0)
     for (int k = NV - 1; k >= 0; --k)
@@ -386,96 +364,29 @@ constexpr int kMaxCh = MPC_PARSE_CHUNKS;  // read chunks per parse workgroup, ta
 // would hold more (LDS budget), smaller windows never hold more than WIN
 template <int WIN> constexpr int tok_cap() { return WIN <= 1024 ? WIN : 1024; }
 
-// K_parse may stage a window's cs bytes by LDS-DMA (global_load_lds_dwordx4,
-// no VGPRs) into the other of two per-wave stage buffers while the current
-// window's rounds run.  Off: measured slower at every config (C1 +15 %, C5
-// +14 %, C2-C4 +1 %; profiles/r04_experiments/kparse_variants.txt) -- the
-// consumer's vmcnt(0) also waits for every event store the rounds issued.
-#ifndef MPC_PARSE_DMA
-#define MPC_PARSE_DMA 0
-#endif
-template <int WIN> constexpr bool parse_dma() { return MPC_PARSE_DMA && WIN >= 1024; }
-
-// K_parse tally modes (bit TM) whose rounds try the fast decode first.  Round
-// 4: modes 3-4 only (C4 -4.5 %, C5 -2 %, C3 +0.6 %, C2 (mode 1) +8 %: every
-// read starts with the empty tokens "Z" ":", which sent its round to the
-// general decode).  Round 5, with those tokens decoded as no-ops on the fast
-// path: every mode (C2 parse 137.9 -> 133.7 us, C1 -1 %, modes 3-4 +-0.2 %;
-// profiles/r05_experiments/place2_fdall_*.log)
-#ifndef MPC_FAST_DECODE_MODES
-#define MPC_FAST_DECODE_MODES 0x1f
-#endif
-template <int TM> constexpr bool fast_decode() { return (MPC_FAST_DECODE_MODES >> TM) & 1; }
+// Every round tries the fast decode first, in every tally mode (the empty
+// tokens "Z" ":" that start each read decode as no-ops on it).
 // Tally mode 3 with ONE substitution window (references up to 16384 bases:
 // C3, C4): the K_parse<3, WIN, NK, true> instantiation takes the round's
 // substitution slots from a wave-uniform count -- no loop over windows, no
 // count kept in a VGPR lane (C3 -1.3 to -1.9 %, C4 -2.2 %); plans with more
-// windows (C5) keep the loop, in a kernel that compiles nothing else
-#ifndef MPC_SUB1
-#define MPC_SUB1 1
-#endif
-// ... and the returning add that takes an insertion event's page slot is
-// issued before the round's other effects (their issue hides its latency)
-#ifndef MPC_EARLY_PLACE
-#define MPC_EARLY_PLACE 0
-#endif
-// ... and tally modes (bit TM) whose next window's cs bytes are loaded before
-// this window's rounds (registers live across them) instead of after
-#ifndef MPC_PREFETCH_CS_MODES
-#define MPC_PREFETCH_CS_MODES 0x00
-#endif
-template <int TM> constexpr bool prefetch_cs() { return (MPC_PREFETCH_CS_MODES >> TM) & 1; }
-// ... and tally modes (bit TM) whose per-unit canonical check is computed as
-// VALU integers with one compare (a '*' then needs all its operand bytes to be
-// bases, not only the last: the others take the general decode)
-#ifndef MPC_INT_CHECK_MODES
-#define MPC_INT_CHECK_MODES 0x00
-#endif
-template <int TM> constexpr bool int_check() { return (MPC_INT_CHECK_MODES >> TM) & 1; }
-// ... and insertion events are queued per wave in LDS (kDefQ entries) and
-// placed 64 at a time, one per lane, instead of in every round that holds one
-// (2 KiB windows, tally modes 1 and 3 with one substitution window, when the
-// queues fit the LDS budget)
-#ifndef MPC_DEFER_PLACE
-#define MPC_DEFER_PLACE 1
-#endif
+// windows (C5) keep the loop, in a kernel that compiles nothing else.
+// Deferred placement (K_parse DP): insertion events are queued per wave in LDS
+// (kDefQ entries) and placed 64 at a time, one per lane, instead of in every
+// round that holds one (2 KiB windows, tally modes 1 and 3 with one
+// substitution window, when the queues fit the LDS budget).
+// The variants measured against these and dropped: DESIGN.md §7.
 constexpr int kDefQ = 128;  // queue entries per wave (a power of 2, >= 127)
-// ... and the epilogue flushes the LDS substitution tallies (tally modes 1, 2)
-// with one 64-bit atomic per two codes of a position (off: bit-exact, C1 +6 %,
-// C2 +-0; profiles/r06_experiments/kparse_flush_x2.txt)
-#ifndef MPC_FLUSH_X2
-#define MPC_FLUSH_X2 0
-#endif
-// ... and (tally mode 3 with one substitution window) the 2-byte substitution
-// events too: a ring of kSubQ per wave, written out 128 at a time (two
-// consecutive events per lane) instead of one global store per round
-// (off: bit-exact, but C3 +7.7 %, C4 +6.5 % -- 120 instead of 89 SGPR spills;
-// profiles/r06_experiments/kparse_deferred_subev.txt)
-#ifndef MPC_DEFER_SUBEV
-#define MPC_DEFER_SUBEV 0
-#endif
-constexpr int kSubQ = 256;  // substitution-event ring per wave (a power of 2, >= 191)
-__host__ __device__ constexpr int defer_bytes(int nw, bool subq) {
-  return nw * (kDefQ * 8 + (subq ? kSubQ * 2 : 0));
-}
-// ... and tally modes whose rounds find a unit's read base by an LDS round trip
+__host__ __device__ constexpr int defer_bytes(int nw) { return nw * kDefQ * 8; }
+// Tally modes (bit TM) whose rounds find a unit's read base by an LDS round trip
 // (slot base written by the read's start lane, read back by every lane) instead
 // of a scalar pass over the round's read starts: short reads (C1 / C2) start
 // several reads per round
 #ifndef MPC_LDS_BASE_MODES
 #define MPC_LDS_BASE_MODES 0x07
 #endif
-// ... or by one ds_bpermute from the round's last read-start lane (no LDS slot,
-// no fence; takes precedence over the two above)
-#ifndef MPC_BPERM_BASE_MODES
-#define MPC_BPERM_BASE_MODES 0x00
-#endif
-template <int TM> constexpr bool bperm_base() { return (MPC_BPERM_BASE_MODES >> TM) & 1; }
-template <int TM> constexpr bool lds_base() { return !bperm_base<TM>() && ((MPC_LDS_BASE_MODES >> TM) & 1); }
-__host__ __device__ constexpr bool lds_base_rt(int tm) {
-  return !((MPC_BPERM_BASE_MODES >> tm) & 1) && ((MPC_LDS_BASE_MODES >> tm) & 1);
-}
-template <int WIN> constexpr int stage_bufs() { return parse_dma<WIN>() ? 2 : 1; }
+template <int TM> constexpr bool lds_base() { return (MPC_LDS_BASE_MODES >> TM) & 1; }
+__host__ __device__ constexpr bool lds_base_rt(int tm) { return (MPC_LDS_BASE_MODES >> tm) & 1; }
 
 template <int WIN, bool SV>              // SV: the read-base slots (lds_base modes)
 struct alignas(16) WaveLds {            // per-wave LDS of K_parse
@@ -484,7 +395,7 @@ struct alignas(16) WaveLds {            // per-wave LDS of K_parse
   int32_t s_read[kSlots];               // local read index
   int32_t s_iend[kSlots];               // i_end | bit 30: read has a downstream flank
   int64_t s_end[kSlots];                // cs offset of the read's end
-  uint8_t stage[stage_bufs<WIN>()][WIN + 16];  // window bytes (+16: word reads past the end)
+  uint8_t stage[WIN + 16];              // window bytes (+16: word reads past the end)
   uint8_t ra[WIN / 8];                  // read-start bits, bit = byte
   uint16_t tok[tok_cap<WIN>() + 2 + 64];  // unit starts in [P, C), then the sentinel C; bits 12-14: ':' prefix
                                         // operand length, bit 15: read start (+64: unconditional loads)
@@ -737,12 +648,9 @@ struct WinIn {
   uint32_t uo, dno;  // low words of the flank offsets: only the lengths' signs are needed
   int32_t ts;
 };
-// A lane's cs bytes of a window.  The cs stream is read exactly once:
-// MPC_CS_NT loads it non-temporally (evict-first in the caches), so it does not
-// push the insertion pages being filled out of L2 before their lines are whole.
-#ifndef MPC_CS_NT
-#define MPC_CS_NT 1
-#endif
+// A lane's cs bytes of a window.  The cs stream is read exactly once, so it is
+// loaded non-temporally (evict-first in the caches) and does not push the
+// insertion pages being filled out of L2 before their lines are whole.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint4 nt_load16(const uint8_t* p) {
@@ -751,9 +659,7 @@ __device__ __forceinline__ uint4 nt_load16(const uint8_t* p) {
 }
 template <int CH>
 __device__ __forceinline__ typename Chunk<CH>::T cs_load(const uint8_t* p) {
-  if constexpr (!MPC_CS_NT) {
-    return *reinterpret_cast<const typename Chunk<CH>::T*>(p);
-  } else if constexpr (CH == 32) {
+  if constexpr (CH == 32) {
     U8x32 v;
     v.a = nt_load16(p);
     v.b = nt_load16(p + 16);
@@ -765,11 +671,11 @@ __device__ __forceinline__ typename Chunk<CH>::T cs_load(const uint8_t* p) {
     return make_uint2(v.x, v.y);
   }
 }
-template <int CH, bool DATA = true>
+template <int CH>
 __device__ __forceinline__ WinIn<CH> fetch_window(const ParseArgs& a, int64_t P, int64_t rs0, int l) {
   WinIn<CH> f;
   const int64_t A = P & ~(int64_t)15;
-  if (DATA) f.d = cs_load<CH>(a.cs + A + CH * l);
+  f.d = cs_load<CH>(a.cs + A + CH * l);
   const int64_t r = rs0 + l;
   const bool ok = r <= a.n_reads;
   f.o = ok ? a.cs_off[r] : INT64_MAX;
@@ -777,21 +683,6 @@ __device__ __forceinline__ WinIn<CH> fetch_window(const ParseArgs& a, int64_t P,
   f.dno = ok ? reinterpret_cast<const uint32_t*>(a.down_off)[2 * r] : 0u;
   f.ts = r < a.n_reads ? a.tstart[r] : 0;
   return f;
-}
-// 1 KiB of global memory at src (16 B per lane) into LDS at dst (wave-uniform
-// byte address), by LDS-DMA: no VGPR destination; the hardware counts it on
-// vmcnt, the compiler does not (the consumer waits vmcnt(0) itself).  M0 is
-// written and restored inside the one statement (cdna_hip_programming.md).
-__device__ __forceinline__ void dma_1k(const uint8_t* src, uint32_t dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src + 16 * lane()), "s"(dst) : "memory");
-}
-template <int WIN>
-__device__ __forceinline__ void dma_window(const uint8_t* src, uint8_t* stage) {
-  const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)stage);
-#pragma unroll
-  for (int k = 0; k < WIN / 1024; ++k) dma_1k(src + 1024 * k, dst + 1024u * k);
 }
 __device__ __forceinline__ void chunk_load(const uint8_t* p, uint4& v) { v = *reinterpret_cast<const uint4*>(p); }
 __device__ __forceinline__ void chunk_load(const uint8_t* p, uint2& v) { v = *reinterpret_cast<const uint2*>(p); }
@@ -814,15 +705,12 @@ __device__ __forceinline__ void chunk_store(uint8_t* p, U8x32 v) {
 // (slot > 64, their adds are discarded by the publish) wait for the new page
 // and try again.  W lives in LDS (tally modes 0-3) or HBM (mode 4).  Every
 // wave reaches the loop's end: an opener never waits.
-// EARLY: the returning add was issued by the caller (`old`), ahead of the
-// round's other effects, so its LDS latency overlaps them.
-template <bool GLOBAL_W, bool EARLY = false>
+template <bool GLOBAL_W>
 __device__ __forceinline__ void parse_place_event(const ParseArgs& a, bool has, uint32_t* W, uint32_t* npg,
-                                                  int64_t pbase, uint32_t* pg0, uint32_t pcap, int b, uint32_t word,
-                                                  uint32_t old = 0u) {
+                                                  int64_t pbase, uint32_t* pg0, uint32_t pcap, int b, uint32_t word) {
   // common case straight-line: the add gives a slot of the current page
   // (pg0 = the workgroup's first page: 32-bit offsets from a scalar base)
-  if constexpr (!EARLY) old = has ? atomicAdd(W, 1u) : 0u;
+  uint32_t old = has ? atomicAdd(W, 1u) : 0u;
   const bool fast = has && (old & ((1u << kPgBits) - 1u)) < (uint32_t)kPgEv;
   if (fast) pg0[(old >> kPgBits) * kPgEv + (old & ((1u << kPgBits) - 1u))] = word;
   bool need = has && !fast;
@@ -908,21 +796,10 @@ __device__ void parse_epilogue(const ParseArgs& a, int n, int gb, int nbk, uint3
       if (dv) atomicAdd(a.diff + gb + p, dv);
     }
     uint32_t* sg = a.sub + (int64_t)gb * 4;
-    if (MPC_FLUSH_X2) {
-      // two codes per 64-bit add (LDS word k = position k/2, codes 2 (k&1) + {0, 1}
-      // = global words 2k, 2k + 1): a position's count of one code never
-      // reaches 2^32, so the low half never carries into the high one
-      for (int k = threadIdx.x; lds_sub && k < 2 * (n + 1); k += blockDim.x) {
-        const uint32_t w2 = sub_l[k];
-        if (w2) atomicAdd(reinterpret_cast<unsigned long long*>(sg) + k,
-                          (unsigned long long)(w2 & 0xffffu) | ((unsigned long long)(w2 >> 16) << 32));
-      }
-    } else {
-      for (int k = threadIdx.x; lds_sub && k < 4 * (n + 1); k += blockDim.x) {  // word k = position k/4, code k%4
-        const uint32_t w2 = sub_l[2 * (k >> 2) + ((k >> 1) & 1)];
-        const uint32_t v = (k & 1) ? (w2 >> 16) : (w2 & 0xffffu);
-        if (v) atomicAdd(sg + k, v);
-      }
+    for (int k = threadIdx.x; lds_sub && k < 4 * (n + 1); k += blockDim.x) {  // word k = position k/4, code k%4
+      const uint32_t w2 = sub_l[2 * (k >> 2) + ((k >> 1) & 1)];
+      const uint32_t v = (k & 1) ? (w2 >> 16) : (w2 & 0xffffu);
+      if (v) atomicAdd(sg + k, v);
     }
   }
   for (int k = threadIdx.x; !big && k < parse_hl_words(n); k += blockDim.x) {
@@ -1007,7 +884,8 @@ __device__ void parse_epilogue(const ParseArgs& a, int n, int gb, int nbk, uint3
 // taken by the workgroups that hold such a read; without NK nothing of it is
 // compiled in (its registers would bound every plan's kernel), and a negative
 // tstart is MPC_DE_UNSUPPORTED (parsed from 0, never an out-of-range write).
-// S1: tally mode 3 with one substitution window (MPC_SUB1 above).
+// S1: tally mode 3 with one substitution window; DP: deferred placement
+// (both described at kDefQ above).
 template <int TM, int WIN, bool NK, bool S1 = false, bool DP = false>
 __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
   static_assert(!S1 || TM == 3, "one substitution window: tally mode 3 only");
@@ -1123,10 +1001,6 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
   // before a round, <= 127 after one)
   uint2* const dq = DP ? reinterpret_cast<uint2*>(lds + a.defer_off) + w * kDefQ : nullptr;
   uint32_t dq_head = 0, dq_tail = 0;
-  // ... and the chunk's substitution events (S1): ring index = event index in
-  // the chunk's region; sq_tail of them are in HBM (nsub_s = the head)
-  constexpr bool DQS = DP && S1 && MPC_DEFER_SUBEV;
-  uint16_t* const sq = DQS ? reinterpret_cast<uint16_t*>(lds + a.defer_off + nw * kDefQ * 8) + w * kSubQ : nullptr;
   auto defer_flush = [&](const int cnt) {  // the cnt (<= 64) oldest events, one per lane
     wave_sync_lds();
     const bool has = l < cnt;
@@ -1143,22 +1017,10 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
   const int64_t sev_base = (P - a.cs_base) / kSubEvBytes + 2 * ra;  // ... and its substitution-event regions (TM 3)
   uint32_t nsub_v = 0;                                    // lane k: substitution events of window k
   uint32_t nsub_s = 0;                                    // ... of the only window (S1, wave-uniform)
-  uint32_t sq_tail = 0;                                   // (DQS) ... written to the region
-  auto sub_flush = [&](const uint32_t cnt) {  // the cnt (<= 128) oldest queued events, two per lane
-    wave_sync_lds();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint32_t k = sq_tail + 2u * (uint32_t)l + (uint32_t)h;
-      if (k < sq_tail + cnt) a.subev[sev_base + k] = sq[k & (kSubQ - 1)];
-    }
-    sq_tail += cnt;
-  };  int64_t rs0 = ra;         // first read whose cs starts at or after P
+  int64_t rs0 = ra;         // first read whose cs starts at or after P
   bool carry = false;       // slot 0 holds a read continuing into this window
   int32_t c_base = 0;       // ... and its coordinate base (wave-uniform): i = base + window prefix of advances
-  constexpr bool dma = parse_dma<WIN>();
-  int sb = 0;               // stage buffer of the current window
-  if (dma && P < wend) dma_window<WIN>(a.cs + (P & ~(int64_t)15), W.stage[0]);
-  WinIn<CH> cur = fetch_window<CH, !dma>(a, P, rs0, l);
+  WinIn<CH> cur = fetch_window<CH>(a, P, rs0, l);
   while (P < wend) {
     const int64_t A = P & ~(int64_t)15;
     // ---- window: at most 63 read starts in [P, E) ----
@@ -1178,16 +1040,11 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
         a.i_end[rs0 + l] = cur.ts < 0 ? 0 : (cur.ts > n ? n + 1 : cur.ts);
       }
       rs0 += 63;
-      cur = fetch_window<CH, !dma>(a, P, rs0, l);  // (same P: the staged bytes stay)
+      cur = fetch_window<CH>(a, P, rs0, l);  // (same P)
       continue;
     }
     // ---- stage bytes, boundary bits ----
-    if (dma) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this window's LDS-DMA has landed
-      chunk_load(W.stage[sb] + CH * l, cur.d);
-    } else {
-      chunk_store(W.stage[0] + CH * l, cur.d);
-    }
+    chunk_store(W.stage + CH * l, cur.d);
     uint32_t spm, cm_own;
     chunk_classes(cur.d, &spm, &cm_own);
     const uint32_t om_own = spm & ~cm_own;
@@ -1279,15 +1136,9 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
       W.s_read[q] = (int32_t)(rs0 + l);
       W.s_iend[q] = (ts < 0 ? 0 : (ts > n ? n + 1 : ts)) | (dn ? 1 << 30 : 0);
     }
-    // ---- the next window starts at C: its bytes go by LDS-DMA into the other
-    // stage buffer now, behind this window's rounds (its read records load
-    // after the rounds: holding them across the rounds costs VGPRs) ----
+    // ---- the next window starts at C (its bytes and read records load after
+    // this window's rounds: holding them across the rounds costs VGPRs) ----
     const int64_t Pn = C, rsn = rs0 + nst;
-    if (dma && Pn < wend) dma_window<WIN>(a.cs + (Pn & ~(int64_t)15), W.stage[sb ^ 1]);
-    // (prefetch_cs: the next window's cs bytes load now, behind the rounds,
-    // into registers that stay live across them; its read records after them)
-    typename Chunk<CH>::T nxt_d{};
-    if (prefetch_cs<TM>() && !dma && Pn < wend) nxt_d = cs_load<CH>(a.cs + (Pn & ~(int64_t)15) + CH * l);
     // ---- token list: starts in [P, C) (bit 15 = read start), then the sentinel ----
     int T;
     {
@@ -1382,7 +1233,7 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
       // other unit ('Z', empty / long operands, non-digits, non-bases, a token
       // past the window, a read not starting with an operator) takes the
       // general decode below for all its lanes.
-      const uint32_t* b32 = reinterpret_cast<const uint32_t*>(W.stage[sb]);
+      const uint32_t* b32 = reinterpret_cast<const uint32_t*>(W.stage);
       int adv0, adv, kind, olen_e;
       uint32_t pay, err = 0u;
       bool fast = false;
@@ -1423,18 +1274,9 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
         // (:309: the operator is only applied to a non-empty operand); no prefix
         // can precede it ('Z' / ':' / '*' / '+' / '-' are never absorbed digits)
         const bool nop = (olen == 0) & !last & (pl == 0) & (colon | star | plus | minus | (op == 'Z'));
-        if constexpr (int_check<TM>()) {  // VALU integers and one compare
-          const uint32_t not4 = (uint32_t)(olen - 1) >> 2;  // 0 iff 1 <= olen <= 4
-          const uint32_t dbad = (((Tx & 0x7F7F7F7Fu) + 0x76767676u) | Tx) & 0x80808080u & cvm;
-          const uint32_t bbad = (star | plus) ? (bad & vm) : 0u;
-          const uint32_t obad = (colon | star | plus | minus) ? 0u : 1u;
-          fast = !v | (!lfar & (((not4 | dbad | bbad | obad) == 0u) | nop));
-          (void)dig;
-        } else {
-          fast = !v | (!lfar & ((olen >= 1) & (olen <= 4) & dig &
-                                (colon | minus | (star & (((bad >> shl) & 0xffu) == 0u)) | (plus & ((bad & vm) == 0u))) |
-                                nop));
-        }
+        fast = !v | (!lfar & ((olen >= 1) & (olen <= 4) & dig &
+                              (colon | minus | (star & (((bad >> shl) & 0xffu) == 0u)) | (plus & ((bad & vm) == 0u))) |
+                              nop));
         // branch-free: '*' 0x2A -> 2, '+' 0x2B -> 3, '-' 0x2D -> 4 from op & 7;
         // ':' -> 1 when it matches at least one base (:77); a no-op: 0
         const int mv = -(int)(v & !nop), mc = -(int)colon;
@@ -1520,20 +1362,14 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
       const int atot = wave_last_i32(ainc);
       // read bases, i = base + G + aex: lanes before the round's first read
       // start continue the open read (base cb); a read starting at lane j has
-      // base tstart - (G + aex_j) on lanes j.. up to the next start.  One
-      // scalar pass over the start lanes (about one per round: reads hold tens
-      // to hundreds of units) instead of an LDS write, fence and read back
+      // base tstart - (G + aex_j) on lanes j.. up to the next start.  Tally
+      // modes with short reads (lds_base: several starts per round) take the
+      // base from the read's slot in LDS, written by its start lane; the
+      // others make one scalar pass over the start lanes (about one per round:
+      // reads hold tens to hundreds of units), with no LDS write, fence and
+      // read back
       int bv = cb;
-      if constexpr (bperm_base<TM>()) {
-        // the last read start at or below this lane (its base by one
-        // ds_bpermute), else the read open since an earlier round (cb)
-        const uint64_t le = brs & (~0ull >> (63 - l));
-        const int mine = q_ts - (G + aex);
-        const int ls = le ? 63 - __clzll((long long)le) : 0;
-        const int sv = __builtin_amdgcn_ds_bpermute(ls << 2, mine);
-        bv = le ? sv : cb;
-        if (brs) cb = __builtin_amdgcn_readlane(mine, 63 - __clzll((long long)brs));
-      } else if constexpr (lds_base<TM>()) {
+      if constexpr (lds_base<TM>()) {
         if (is_rs) W.s_val[q] = q_ts - (G + aex);
         wave_sync_lds();
         const int sv = W.s_val[q];
@@ -1581,8 +1417,6 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
       const bool ok = te == 0 && !wo_ins;
       const bool ins_inline = ((kind == 3 && olen_e <= kInsInline) || wrap) && ok;
       const bool any_ins = ballot(ins_inline) != 0;  // (wave-uniform)
-      uint32_t pold = 0u;
-      if (!DP && MPC_EARLY_PLACE && any_ins && ins_inline) pold = atomicAdd(bkw + gi / kBW, 1u);  // slot in its bucket's page
       if (ok & (kind == 2) & !wrap & (TM != 3 || (!S1 && a.sub_wins == 0))) odd_sub(i, (int)pay);  // (S1: one window)
       const bool del = NEG ? ok & (kind == 4) & (di < n) & (i + olen_e > di) : ok & (kind == 4) & (i >= 0) & (i < n);
       if (del) {
@@ -1595,11 +1429,7 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
         const bool sev = ok && kind == 2 && !wrap;
         const uint64_t bw = ballot(sev);
         const uint16_t ev = (uint16_t)(((uint32_t)i << 2) | pay);
-        if (DQS) {
-          if (sev) sq[(nsub_s + lanes_below(bw)) & (kSubQ - 1)] = ev;
-        } else {
-          if (sev) a.subev[sev_base + nsub_s + lanes_below(bw)] = ev;
-        }
+        if (sev) a.subev[sev_base + nsub_s + lanes_below(bw)] = ev;
         nsub_s += (uint32_t)__popcll(bw);
       } else if (TM == 3 && a.sub_wins > 0) {  // substitution events, wave-aggregated per window
         const bool sev = ok && kind == 2 && !wrap;
@@ -1620,8 +1450,8 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
           dq[(dq_head + lanes_below(bi)) & (kDefQ - 1)] = make_uint2((uint32_t)(gi / kBW), ins_word(gi, li, pay, rl - (int)r0));
         dq_head += (uint32_t)__popcll(bi);
       } else if (any_ins) {  // the event into its bucket's page (written once)
-        parse_place_event<big, MPC_EARLY_PLACE != 0>(a, ins_inline, bkw + gi / kBW, npg, pbase, pg0, pcap, gi / kBW,
-                                                     ins_word(gi, li, pay, rl - (int)r0), pold);
+        parse_place_event<big>(a, ins_inline, bkw + gi / kBW, npg, pbase, pg0, pcap, gi / kBW,
+                               ins_word(gi, li, pay, rl - (int)r0));
       }
       if (last) {  // the read's last operation: i_end, downstream check, span
         const int ia = i + adv;
@@ -1650,9 +1480,8 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
     // redone on the general decode (one loop: measured against a loop per kind
     // and against per-window canonical checks, profiles/r06_experiments/)
     for (int t0 = 0; t0 < T; t0 += 64) {
-      if (!fast_decode<TM>() || !round(t0, std::false_type{})) round(t0, std::true_type{});
+      if (!round(t0, std::false_type{})) round(t0, std::true_type{});
       if (DP && dq_head - dq_tail >= 64u) defer_flush(64);
-      if (DQS && nsub_s - sq_tail >= 128u) sub_flush(128u);
     }
     wave_sync_lds();
     // ---- reads that ended in this window: i_end; carry the open one ----
@@ -1674,15 +1503,7 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
     wave_sync_lds();
     P = Pn;
     rs0 = rsn;
-    sb ^= dma ? 1 : 0;
-    if (Pn < wend) {
-      if (prefetch_cs<TM>() && !dma) {
-        cur = fetch_window<CH, false>(a, Pn, rsn, l);
-        cur.d = nxt_d;
-      } else {
-        cur = fetch_window<CH, !dma>(a, Pn, rsn, l);
-      }
-    }
+    if (Pn < wend) cur = fetch_window<CH>(a, Pn, rsn, l);
     MPC_SEG(5);
   }
   // reads starting at the range end have an empty cs
@@ -1691,7 +1512,6 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
     flag_read(a, DE_OP, r);
     a.i_end[r] = ts < 0 ? 0 : (ts > n ? n + 1 : ts);
   }
-  if (DQS && nsub_s != sq_tail) sub_flush(nsub_s - sq_tail);  // (<= 127)
   if (TM == 3 && l < a.sub_wins)
     a.subev_cnt[((int64_t)blockIdx.x * kMaxCh + chk) * kMaxSubWins + l] = S1 ? nsub_s : nsub_v;
   }  // chunks
@@ -1704,9 +1524,6 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
   }
   if (DP && dq_head != dq_tail) defer_flush((int)(dq_head - dq_tail));  // (<= 63)
   MPC_SEG(5);
-  // every LDS-DMA was waited for by the window after it (one is issued only
-  // when another window follows); drain anyway before the LDS is reused
-  if (parse_dma<WIN>()) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   MPC_SEG(6);
   parse_epilogue<TM>(a, n, gb, nbk, hl, bkw, uni, npg, pbase, pcap);
@@ -1727,8 +1544,8 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
 // K_subs (tally mode 3): the substitution events of a sample's parse waves for
 // one kSubWin-position window, tallied in LDS as 16-bit counters (the event
 // word IS the counter index: position << 2 | code; a block's chunk holds at most
-// 65535 reads, and a read substitutes a position at most once) and flushed with
-// contiguous atomics.  One block
+// 65535 reads, and a read substitutes a position at most once) and stored as
+// the block's slab row.  One block
 // per (sample, window, chunk of <= kSubsWG parse workgroups); wave v walks the
 // chunk's regions v, v + 16, ... (8 loads in flight per lane).
 // ---------------------------------------------------------------------------
@@ -1736,9 +1553,6 @@ constexpr int kSubsWG = 32;  // parse workgroups per K_subs block, at most
 // K_subs blocks store their 16-bit tallies in a slab row each, reduced per
 // (sample, window) by K_subsum (instead of every block adding its ~4 n counters
 // into the same words with global atomics)
-#ifndef MPC_SUBS_SLAB
-#define MPC_SUBS_SLAB 1
-#endif
 struct SubsArgs {
   const int4* work;    // {sample, window, first parse workgroup, end}
   const int4* pwork;   // parse work table {sample, r0, r1, 0}
@@ -1746,7 +1560,7 @@ struct SubsArgs {
   const int64_t* cs_off; int64_t cs_base;
   const uint16_t* subev; const uint32_t* subev_cnt; int64_t subev_cap;
   const int32_t* n_of; const int32_t* gbase; uint32_t* sub;
-  uint32_t* slab;  // MPC_SUBS_SLAB: [K_subs block][kSubWin * 2] packed tallies
+  uint32_t* slab;  // [K_subs block][kSubWin * 2] packed tallies
   int32_t nw_parse;
 };
 __global__ __launch_bounds__(1024) void K_subs(SubsArgs a) {
@@ -1789,17 +1603,10 @@ __global__ __launch_bounds__(1024) void K_subs(SubsArgs a) {
   }
   __syncthreads();
   const int64_t p0 = (int64_t)win * kSubWin, n = a.n_of[smp];
-  if (MPC_SUBS_SLAB) {  // the window's positions (< n), two words each, coalesced
-    uint32_t* row = a.slab + (int64_t)blockIdx.x * (kSubWin * 2);
-    const int nw2 = (int)(2 * (n - p0 < kSubWin ? n - p0 : kSubWin));
-    for (int j = threadIdx.x; j < nw2; j += blockDim.x) row[j] = cnt[j];
-    return;
-  }
-  uint32_t* dst = a.sub + ((int64_t)a.gbase[smp] + p0) * 4;
-  for (int j = threadIdx.x; j < kSubWin * 4; j += blockDim.x) {  // consecutive lanes, consecutive words
-    const uint32_t x = (cnt[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-    if (x && p0 + (j >> 2) < n) atomicAdd(dst + j, x);
-  }
+  // the window's positions (< n), two words each, coalesced
+  uint32_t* row = a.slab + (int64_t)blockIdx.x * (kSubWin * 2);
+  const int nw2 = (int)(2 * (n - p0 < kSubWin ? n - p0 : kSubWin));
+  for (int j = threadIdx.x; j < nw2; j += blockDim.x) row[j] = cnt[j];
 }
 
 // K_subsum: per (sample, window, 256 slab words): the sum over the window's
@@ -2364,7 +2171,7 @@ __global__ __launch_bounds__(kRunsGB) void K_runs(Dev d, uint32_t epoch) {
   }
   if (w == 0) {
     int64_t pre;
-    lookback<1, MPC_LOOKBACK_U>(reinterpret_cast<uint64_t*>(d.bsum), b, (uint64_t)(epoch & 0x3fffffffu) << 32, &bt, &pre,
+    lookback<1>(reinterpret_cast<uint64_t*>(d.bsum), b, (uint64_t)(epoch & 0x3fffffffu) << 32, &bt, &pre,
                                 &d.status[MPC_ST_FLAGS]);
     if (l == 0) s_pre = pre;
   }
@@ -2406,13 +2213,6 @@ __device__ __forceinline__ int64_t run_left(const int32_t* rs, const int32_t* rs
 // buckets become many units) and appends them to one list.
 // ---------------------------------------------------------------------------
 constexpr int kUB = 1024;             // threads of K_ins and of K_left's default geometry
-// K_left: interpolation probes before the binary search of a gap's staged
-// RIGHT reads (ranges over 16); off: bit-exact, C3 +9 us, C4 +13 us, C2 / C5 +-2 us
-// (profiles/r06_experiments/k_left_search_ablations.txt)
-#ifndef MPC_LEFT_INTERP
-#define MPC_LEFT_INTERP 0
-#endif
-
 constexpr int kLeftVals = 4096;       // mixed RIGHT reads of a bucket staged in K_left's LDS
 constexpr int kEPT = 16;         // events per thread per unit (loads batched)
 constexpr int kUnit = kUB * kEPT;     // events per work unit (K_left<kUB>; K_left<512>: half)
@@ -2585,9 +2385,6 @@ struct LeftArgs {
 // UB = 1024 at most 64 VGPRs, two 16-wave blocks (LDS ~57 KB each; C3 K_left
 // 312 -> 227 us, C4 387 -> 286 us; 5 VGPRs spill); UB = 512 at most 80 VGPRs
 // and a smaller RIGHT-read stage, three 8-wave blocks (C5 285 -> 218 us)
-#ifdef MPC_LEFT_DIAG  // diagnostic builds only: K_left event paths (mpc_diag_left)
-__device__ unsigned long long g_left_diag[8];
-#endif
 template <int UB>  // threads per block; work units of UB * kEPT events
 __global__ __launch_bounds__(UB) __attribute__((amdgpu_waves_per_eu(UB == 1024 ? 8 : 6))) void K_left(LeftArgs a) {
   __shared__ int64_t s_key;
@@ -2705,30 +2502,6 @@ __global__ __launch_bounds__(UB) __attribute__((amdgpu_waves_per_eu(UB == 1024 ?
         if (vl) {  // 32-bit search of the staged RIGHT reads
           int lo = la - v0, hi = lb - v0;
           const int l0 = lo;
-          if (MPC_LEFT_INTERP && hi - lo > 16) {
-            // interpolation probes first (a gap's RIGHT reads are spread over
-            // the batch's read indices): the range's end values, then up to two
-            // probes at the interpolated index; [lo, hi) keeps
-            // s_vals[< lo] < rg <= s_vals[>= hi], so any probe is exact
-            int32_t vL = s_vals[lo], vH = s_vals[hi - 1];
-            if (rg <= vL) {
-              hi = lo;
-            } else if (rg > vH) {
-              lo = hi;
-            } else {  // vL < rg <= vH
-              int aL = lo, aH = hi - 1;
-              lo = aL + 1;
-              hi = aH;
-#pragma unroll
-              for (int it = 0; it < 2; ++it) {
-                if (hi - lo <= 8) break;
-                const float f = __fdividef((float)(rg - vL), (float)(vH - vL));
-                const int g = min(max(aL + (int)(f * (float)(aH - aL)), lo), hi - 1);
-                const int32_t vg = s_vals[g];
-                if (vg < rg) { aL = g; vL = vg; lo = g + 1; } else { aH = g; vH = vg; hi = g; }
-              }
-            }
-          }
           while (lo < hi) {
             const int mid = (lo + hi) >> 1;
             if (s_vals[mid] < rg) lo = mid + 1; else hi = mid;
@@ -2742,15 +2515,6 @@ __global__ __launch_bounds__(UB) __attribute__((amdgpu_waves_per_eu(UB == 1024 ?
       // run's slot hi_run - 1 - bi, :37-62): K_ins maps them to rows after the layout
       // LDS slots: the shard's runs of the gap (as many as on one GPU); the
       // global run is s_rs[p] + g + roff + k
-#ifdef MPC_LEFT_DIAG
-      {  // [0] events [1] searched (mixed gap) [2] run k >= kKMax [3] sum of searched ranges [4] k >= 16 [5] k >= 32
-        atomicAdd(&g_left_diag[0], 1ull);
-        if (lb > la) { atomicAdd(&g_left_diag[1], 1ull); atomicAdd(&g_left_diag[3], (unsigned long long)(lb - la)); }
-        if (k >= kKMax) atomicAdd(&g_left_diag[2], 1ull);
-        if (k >= 16) atomicAdd(&g_left_diag[4], 1ull);
-        if (k >= 32) atomicAdd(&g_left_diag[5], 1ull);
-      }
-#endif
       if (k < kKMax) {
         // the run's longest LEFT string: UB = 1024 takes it from the highest
         // slot holding a base at the flush (one LDS atomic less per event: C4
@@ -3223,7 +2987,7 @@ __global__ __launch_bounds__(kGB) void K_layout(Dev d, uint32_t epoch) {
   if (w == 0) {  // [2 nb] words: block b's rows word, diff word
     const int32_t own[2] = {br, bd};
     int64_t pre[2];
-    lookback<2, MPC_LOOKBACK_U>(reinterpret_cast<uint64_t*>(d.bsum), b, tag, own, pre, &d.status[MPC_ST_FLAGS]);
+    lookback<2>(reinterpret_cast<uint64_t*>(d.bsum), b, tag, own, pre, &d.status[MPC_ST_FLAGS]);
     if (l == 0) { s_pre[0] = pre[0]; s_pre[1] = pre[1]; }
   }
   __syncthreads();
@@ -3852,7 +3616,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void K
   const uint64_t tag = (uint64_t)(epoch & 0x3fffffffu) << 32;
   if (w == 0) {
     int64_t pr;
-    lookback<1, MPC_LOOKBACK_U>(reinterpret_cast<uint64_t*>(d.ksum), b, tag, &bt, &pr, &d.status[MPC_ST_FLAGS]);
+    lookback<1>(reinterpret_cast<uint64_t*>(d.ksum), b, tag, &bt, &pr, &d.status[MPC_ST_FLAGS]);
     if (l == 0) s_pre = pr;
   }
   __syncthreads();
@@ -4021,7 +3785,7 @@ static const void* parse_kernel_t(int tm, int win, bool s1) {
 }
 // the plan's K_parse: with the negative-start rounds only when it holds such reads
 static const void* parse_kernel(const mpc_plan* p) {
-  const bool s1 = MPC_SUB1 && p->tally_mode == 3 && p->sub_wins == 1;
+  const bool s1 = p->tally_mode == 3 && p->sub_wins == 1;
   if (p->defer_off > 0)  // (planner: 2 KiB windows, tally mode 1 or 3 with s1, no negative starts)
     return p->tally_mode == 1 ? (const void*)K_parse<1, 2048, false, false, true>
                               : (const void*)K_parse<3, 2048, false, true, true>;
@@ -4038,15 +3802,13 @@ static void launch_subs(const mpc_plan* p, const Dev& d, hipStream_t st) {
   a.wave_tab = at<const int32_t>(p, mpc_plan::B_WWAVE);
   a.slab = at<uint32_t>(p, mpc_plan::B_SUBSLAB);
   hipLaunchKernelGGL(K_subs, dim3((unsigned)(p->work_sub.size() / 4)), dim3(1024), 0, st, a);
-  if (MPC_SUBS_SLAB) {
-    const dim3 g((unsigned)(p->work_subsum.size() / 4 * (kSubWin * 2 / kSumCols)));
-    if (p->subsum_rows > 8)
-      hipLaunchKernelGGL(K_subsum<4>, g, dim3(4 * kSumCols), 0, st, at<const int4>(p, mpc_plan::B_WSUBSUM),
-                         (const uint32_t*)a.slab, d.n_of, d.gbase, d.sub);
-    else
-      hipLaunchKernelGGL(K_subsum<1>, g, dim3(kSumCols), 0, st, at<const int4>(p, mpc_plan::B_WSUBSUM),
-                         (const uint32_t*)a.slab, d.n_of, d.gbase, d.sub);
-  }
+  const dim3 g((unsigned)(p->work_subsum.size() / 4 * (kSubWin * 2 / kSumCols)));
+  if (p->subsum_rows > 8)
+    hipLaunchKernelGGL(K_subsum<4>, g, dim3(4 * kSumCols), 0, st, at<const int4>(p, mpc_plan::B_WSUBSUM),
+                       (const uint32_t*)a.slab, d.n_of, d.gbase, d.sub);
+  else
+    hipLaunchKernelGGL(K_subsum<1>, g, dim3(kSumCols), 0, st, at<const int4>(p, mpc_plan::B_WSUBSUM),
+                       (const uint32_t*)a.slab, d.n_of, d.gbase, d.sub);
 }
 static void launch_parse(const mpc_plan* p, const Dev& d, hipStream_t st) {
   ParseArgs a = parse_args(p, d);
@@ -4076,13 +3838,11 @@ static UnitArgs unit_args(const mpc_plan* p, const Dev& d) {
 
   return a;
 }
-// K_left's geometry (planner: left_ub)
-static void launch_left(const mpc_plan* p, const Dev& d, hipStream_t st);
+// K_left's geometry (planner: left_ub):
 // two (1024-thread) or three (512-thread) resident blocks per CU
 static int64_t left_grid(const mpc_plan* p) {
   return std::max<int64_t>(1, std::min<int64_t>(p->units_cap, p->left_ub == 512 ? 768 : 512));
 }
-static LeftArgs left_args(const mpc_plan* p, const Dev& d);
 static void launch_left(const mpc_plan* p, const Dev& d, hipStream_t st) {
   if (p->left_ub == 512) hipLaunchKernelGGL(K_left<512>, dim3(left_grid(p)), dim3(512), 0, st, left_args(p, d));
   else hipLaunchKernelGGL(K_left<kUB>, dim3(left_grid(p)), dim3(kUB), 0, st, left_args(p, d));
@@ -4167,16 +3927,6 @@ static inline unsigned nblk(int64_t n, int b = 256) {
 extern "C" {
 
 int mpc_version(void) { return MPC_ABI_VERSION; }
-#ifdef MPC_LEFT_DIAG
-int mpc_diag_left(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_left_diag), sizeof(g_left_diag)) != hipSuccess) return -1;
-  if (reset) {
-    static const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_left_diag), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
 
 int mpc_build_flags(void) { return MPC_BF_STAMPS_ | MPC_BF_TUNING_ | MPC_BF_VARIANT_; }
 
@@ -4420,10 +4170,10 @@ int mpc_plan_create(const mpc_input* in, int64_t row_cap, mpc_plan** out) {
     }
     // deferred placement: the per-wave queues after the parse LDS, when they fit
     p->defer_off = 0;
-    if (MPC_DEFER_PLACE && p->parse_win == 2048 && p->in.neg_reads == 0 &&
-        (p->tally_mode == 1 || (MPC_SUB1 && p->tally_mode == 3 && p->sub_wins == 1))) {
+    if (p->parse_win == 2048 && p->in.neg_reads == 0 &&
+        (p->tally_mode == 1 || (p->tally_mode == 3 && p->sub_wins == 1))) {
       const int off = (p->parse_lds + 15) & ~15;
-      const int end = off + defer_bytes(p->parse_nw, MPC_DEFER_SUBEV && p->tally_mode == 3);
+      const int end = off + defer_bytes(p->parse_nw);
       if (end <= lds_cap && std::max(1, std::min(lds_cap / end, max_waves_cu / p->parse_nw)) == per_cu) {
         p->defer_off = off;
         p->parse_lds = end;
@@ -4523,7 +4273,7 @@ int mpc_plan_create(const mpc_input* in, int64_t row_cap, mpc_plan** out) {
   set(mpc_plan::B_WSUB, (int64_t)p->work_sub.size(), 4);
   set(mpc_plan::B_BKCUR, p->tally_mode == 4 ? (int64_t)p->n_parse_wg * p->nbmax : 0, 4);
   set(mpc_plan::B_WWAVE, (int64_t)p->work_wave.size(), 4);
-  set(mpc_plan::B_SUBSLAB, MPC_SUBS_SLAB ? (int64_t)(p->work_sub.size() / 4) * kSubWin * 2 : 0, 4);
+  set(mpc_plan::B_SUBSLAB, (int64_t)(p->work_sub.size() / 4) * kSubWin * 2, 4);
   set(mpc_plan::B_WSUBSUM, (int64_t)p->work_subsum.size(), 4);
   set(mpc_plan::B_WOEV, p->wo_cap, sizeof(WoEv));
   set(mpc_plan::B_WOKEY, p->wo_cap ? p->wo_p2 : 0, 8);

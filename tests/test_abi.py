@@ -76,7 +76,7 @@ def test_planner_geometry(pkg):
 
 def test_planner_deferred_placement(pkg):
     """K_parse queues insertion events per wave in LDS (mpc_kernels.hip
-    MPC_DEFER_PLACE) only with 2 KiB windows in tally mode 1 or 3 with one
+    K_parse DP, kDefQ) only with 2 KiB windows in tally mode 1 or 3 with one
     substitution window, and only when the queues fit the LDS budget without
     changing the geometry: C2-C4 take it, C1 and C5 (LDS full) do not; reads
     with negative starts keep inline placement (the plan binds that K_parse)."""
