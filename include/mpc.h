@@ -196,7 +196,9 @@ const char* mpc_last_error(void);
 /* Plan for one input shape.  row_cap = capacity of the pileup-row buffers; the
  * exact need is only known on device after the layout phase (status word
  * MPC_ST_ROWS_NEEDED) -- if it is exceeded, MPC_DE_CAPACITY is raised and the
- * caller re-plans with a larger row_cap.  Host-only, no device work. */
+ * caller re-plans with a larger row_cap.  Host-only, no device work
+ * (csrc/mpc_plan.cpp: plain C++, as every call here that takes no stream but
+ * mpc_plan_bind). */
 int mpc_plan_create(const mpc_input* in, int64_t row_cap, mpc_plan** plan);
 int mpc_plan_destroy(mpc_plan* plan);
 /* Host copies of the parse work split (tests / tools; no device work):

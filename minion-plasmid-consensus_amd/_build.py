@@ -1,13 +1,15 @@
 """In-tree builds of the native libraries (no JIT cache: the .so files travel with
 the repo snapshot to the GPU box).
 
-  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan), hipcc --offload-arch=gfx950
+  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan), hipcc --offload-arch=gfx950;
+                   its host planner (csrc/mpc_plan.cpp) with g++
   libmpc_synth.so  host-only synthetic data generator (g++)
   libmpc_ingest.so native host I/O: ingest (Steps 1-3) and writers (Step 7) (include/mpc_ingest.h, g++ -pthread)
                    and the host half of verify_consensus (include/mpc_verify.h)
 """
 import os
 import subprocess
+import tempfile
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
@@ -18,7 +20,8 @@ LIBSYNTH = os.path.join(PKG, "libmpc_synth.so")
 LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 
 HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip"]
-HIP_HEADERS = ["mpc_device.h"]
+HOST_SOURCES = ["mpc_plan.cpp"]  # libmpc.so's host planner (g++, no HIP)
+HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h"]
 
 
 def _stale(target, sources):
@@ -52,12 +55,18 @@ def build_hip(force=False, extra=(), out=None):
     """libmpc.so (``out``/``extra``: experiment variants, e.g. -DMPC_TUNING_OVERRIDES)."""
     out = out or LIBMPC
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h")]
+    host = [os.path.join(CSRC, s) for s in HOST_SOURCES]
+    deps = srcs + host + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h")]
     if force or extra or _stale(out, deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-               "-I", INCLUDE, "-I", CSRC, "-o", out] + list(extra) + srcs
-        subprocess.run(cmd, check=True)
+        flags = ["-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC] + list(extra)
+        with tempfile.TemporaryDirectory() as tmp:
+            objs = []
+            for s in host:  # the host planner: plain C++, same -D switches as the kernels
+                objs.append(os.path.join(tmp, os.path.splitext(os.path.basename(s))[0] + ".o"))
+                subprocess.run(["g++", "-c"] + flags + ["-o", objs[-1], s], check=True)
+            # (objects before the .hip sources: hipcc reads everything after one as HIP)
+            subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-o", out] + flags + objs + srcs, check=True)
     return out
 
 

@@ -24,13 +24,16 @@
 //   consensus K_call         per-slot top/second/tie/N (:363-439), max depth
 //             K_select       threshold test + ordered compaction of the calls
 //                            (look-back scan)
+//
+// This file: the kernels, then binding a plan to its workspace, the launches
+// and the phases of the C-ABI.  The host planner (mpc_plan_create and every
+// entry point that touches no device) is mpc_plan.cpp / mpc_plan.h; the
+// constants and sizing functions planner and kernels share are mpc_geometry.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
-#include <cstdio>
 #include <cstring>
-#include <cstdlib>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -58,7 +61,12 @@
 #define MPC_BF_VARIANT_ 0
 #endif
 
+// (after the record above: mpc_geometry.h gives two of those switches their defaults)
+#include "mpc_geometry.h"
+#include "mpc_plan.h"
+
 using namespace mpc;
+using namespace mpc_geom;
 
 namespace {
 
@@ -74,8 +82,7 @@ constexpr int kInsInline = 4;       // insertions up to this length travel as on
 // prefix of advances stays below (WIN / 8) * 2^22 <= 2^30 at the largest
 // window, and a coordinate (a read base <= kICap plus that prefix plus one
 // unit's advance) below 2^31 (static_assert below).  The insertion event word
-// holds the gap in 22 bits (kNullGap).
-constexpr int kMaxRefLen = (1 << 22) - 2;
+// holds the gap in 22 bits (kNullGap).  Hence kMaxRefLen (mpc_geometry.h).
 constexpr int kAdvCap = 1 << 22;    // > any reference length: a clamped advance keeps i past the end
 constexpr int kICap = 1 << 28;      // saturation of the running coordinate i
 constexpr int kMaxWin = 2048;       // largest parse window (bytes)
@@ -83,8 +90,6 @@ static_assert((int64_t)kICap + (int64_t)(kMaxWin / 8) * kAdvCap + 2 * (int64_t)k
               "32-bit coordinates: read base + window prefix of advances + one unit");
 static_assert((int64_t)MPC_TSTART_MIN - (int64_t)(kMaxWin / 8) * kAdvCap > (int64_t)INT32_MIN,
               "32-bit coordinates below 0 (negative target starts)");
-constexpr int kBW = 64;             // gaps per insertion bucket (K_left workgroup)
-static_assert(kBW <= 64 && (kBW & (kBW - 1)) == 0, "sorted insertion events hold the gap within its bucket in 6 bits");
 constexpr int kKMax = 8;            // runs per gap tallied in K_left's LDS (others go to HBM)
 constexpr uint32_t kNullGap = 0x3fffffu;
 // decoupled look-back status words (K_layout, K_select): flag in bits 62-63
@@ -144,53 +149,8 @@ __device__ void lookback(uint64_t* st, int64_t b, uint64_t tag, const int32_t* o
   for (int k = 0; k < NV; ++k) pre[k] = acc[k];
 }
 
-struct Ovf {  // long insertion (len > kInsInline), tallied by K_flank
-  int64_t off;  // absolute byte offset of the inserted bases in cs
-  int32_t read;
-  int32_t gap;  // local gap index (i), sample implied by read
-  int32_t len;
-  int32_t pad[3];
-};
-
-// A string Python's negative index wrap writes into an ODD position: with i in
-// [-n, 0), obsarr[2 i] is obsarr[2 (n + i) + 1], the reference base n + i.  An
-// upstream flank at tstart = i (:303) or a '+' at i (:81-87) is a LEFT string
-// there, the downstream flank of a read ending at i (:323) a RIGHT string.
-// K_parse lists them (rare: minimap2 never writes a negative start); the
-// position's slot list is then replayed like a gap's (K_woprep, K_wocover,
-// K_layout<true>, K_worows).
+// WoEv.type of a string in a wrapped odd position (the records: mpc_geometry.h)
 enum { kWoUp = 0, kWoIns = 1, kWoDown = 2 };  // (order within one read: upstream, cs, downstream)
-struct WoEv {
-  int32_t g;     // global index of the odd position: gbase[s] + (n + i)
-  int32_t read;  // local read
-  int32_t len;   // '+': operand bytes (flanks: from the read's offsets)
-  int32_t type;  // kWo*
-  int64_t src;   // '+': absolute cs offset of the operand
-};
-struct WoPos {   // one odd position holding such strings
-  int32_t g, beg, end;  // its events [beg, end) in the sorted list
-  int32_t run0, nrun;   // its runs (LEFT events between consecutive RIGHT ones)
-  int32_t lo, F, row0;  // replayed lo, slots, first row (K_layout<true>)
-};
-struct WoRun {
-  int32_t M, R;         // longest LEFT string of the run / RIGHT string closing it
-  int32_t hiR, loR;     // replayed hi seen by its LEFT events / lo seen by its RIGHT event
-  uint32_t C[4];        // one-base LEFT writes of the reads covering the position (:79, :96)
-};
-constexpr int64_t kWoCapMax = 1 << 22;  // event list bound (the single-workgroup sort)
-// What a shard sends of a WoEv (n_shards > 1, K_wopack): nothing in it points
-// into the owner's buffers.  A flank's length comes from the owner's up_off /
-// down_off, which no other shard holds, so it travels here.  Record 0 of the
-// gathered list is a header: its g is the number of records behind it.
-struct WoRec {
-  int32_t g;      // as WoEv
-  int32_t gread;  // global read: read_offset + local read (< 2^30)
-  int32_t len;    // string length (flanks included)
-  int32_t type;   // kWo*
-  int32_t shard;  // the owner
-  int32_t ev;     // index in the owner's WoEv list
-};
-static_assert(sizeof(WoRec) == 24, "exchanged as 6 int32 (mpc.h MPC_BUF_WRAP_REC)");
 
 // Insertion events (what K_left reads): 4 bytes, bases (8 bits, 2 per base in
 // string order) | (len-1) << 8 | gap within its kBW-gap bucket << 10 | read
@@ -199,7 +159,7 @@ static_assert(sizeof(WoRec) == 24, "exchanged as 6 int32 (mpc.h MPC_BUF_WRAP_REC
 // event lies in: K_parse places every event once, into 64-event pages of its
 // (workgroup, bucket), allocated as they fill (parse_place_event); the
 // epilogue lists every bucket's pages, all full but the last (pg_list).
-constexpr int kPgEv = 64;                    // events per page (256 B)
+// (kPgEv events per page, parse_page_base: mpc_geometry.h)
 constexpr int kPgBits = 12;                  // bucket word: page << 12 | fill
 constexpr uint32_t kPgNone = 0xFFFFFu;       // page field of a bucket with no page yet
 constexpr uint32_t kPgOvf = kPgNone - 1u;    // ... of a bucket whose workgroup ran out of pages (DE_INTERNAL)
@@ -208,12 +168,6 @@ constexpr uint32_t kPgMark = 0xFFFFFFFFu;    // pg_own of a bucket's last page (
 static_assert(kPgEv + 1024 < (1 << kPgBits), "fill field: a full page plus every thread of a block waiting");
 __device__ __forceinline__ uint32_t ins_word(int gap, int len, uint32_t bases, int rel_read) {
   return bases | ((uint32_t)(len - 1) << 8) | (((uint32_t)gap % (uint32_t)kBW) << 10) | ((uint32_t)rel_read << 16);
-}
-// page base (in pages) of parse workgroup wg: its events are at most half its
-// cs bytes plus 3 per read (an insertion takes >= 2 cs bytes), i.e. at most
-// bytes / 128 + 3 reads / 64 full pages, plus one partial page per bucket
-__host__ __device__ inline int64_t parse_page_base(int64_t cs_rel, int64_t r, int64_t wg, int nbs) {
-  return cs_rel / 128 + (3 * r) / 64 + wg * (int64_t)(nbs + 4);
 }
 
 struct Dev {  // device-side views of the plan for the small kernels (passed by value)
@@ -265,9 +219,7 @@ struct Dev {  // device-side views of the plan for the small kernels (passed by 
   double mdf, gtf;
 };
 static_assert(sizeof(void*) == sizeof(int64_t), "Dev layout");
-// this shard's records; all shards' records behind a header; per run "some
-// read of this shard has a one-base write" (each starts 256-byte aligned)
-__host__ __device__ inline int64_t wo_a256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+// the three exchange buffers behind wo_x (each starts 256-byte aligned: wo_a256)
 __device__ __forceinline__ WoRec* wo_rec(const Dev& d) { return reinterpret_cast<WoRec*>(d.wo_x); }
 __device__ __forceinline__ const WoRec* wo_all(const Dev& d) {
   return reinterpret_cast<const WoRec*>(d.wo_x + wo_a256(d.wo_cap * (int64_t)sizeof(WoRec)));
@@ -355,14 +307,8 @@ __device__ uint64_t g_stamps[kStampWaves * kStampSeg];
 // ---------------------------------------------------------------------------
 // K_parse: Step 4 of the reference (:285-323 tokenizer, :74-104 processOperation)
 // ---------------------------------------------------------------------------
-constexpr int kSlots = 64;              // reads touching a window (slot 0 = read carried in)
-constexpr int kMaxPW = 16;              // waves per workgroup (runtime: blockDim.x / 64)
+// (kSlots, kMaxPW, kMaxCh, tok_cap, WaveLds and the LDS sizing: mpc_geometry.h)
 constexpr uint32_t kFar = 0x7fffu;      // sentinel: the window's only token ends beyond the window
-constexpr int kMaxCh = MPC_PARSE_CHUNKS;  // read chunks per parse workgroup, taken dynamically by its waves
-
-// units per window (tok list capacity): a 2 KiB window is cut early when it
-// would hold more (LDS budget), smaller windows never hold more than WIN
-template <int WIN> constexpr int tok_cap() { return WIN <= 1024 ? WIN : 1024; }
 
 // Every round tries the fast decode first, in every tally mode (the empty
 // tokens "Z" ":" that start each read decode as no-ops on it).
@@ -371,35 +317,10 @@ template <int WIN> constexpr int tok_cap() { return WIN <= 1024 ? WIN : 1024; }
 // substitution slots from a wave-uniform count -- no loop over windows, no
 // count kept in a VGPR lane (C3 -1.3 to -1.9 %, C4 -2.2 %); plans with more
 // windows (C5) keep the loop, in a kernel that compiles nothing else.
-// Deferred placement (K_parse DP): insertion events are queued per wave in LDS
-// (kDefQ entries) and placed 64 at a time, one per lane, instead of in every
-// round that holds one (2 KiB windows, tally modes 1 and 3 with one
-// substitution window, when the queues fit the LDS budget).
+// Deferred placement (K_parse DP, kDefQ) and the tally modes that find a
+// unit's read base by an LDS round trip (MPC_LDS_BASE_MODES): mpc_geometry.h.
 // The variants measured against these and dropped: DESIGN.md §7.
-constexpr int kDefQ = 128;  // queue entries per wave (a power of 2, >= 127)
-__host__ __device__ constexpr int defer_bytes(int nw) { return nw * kDefQ * 8; }
-// Tally modes (bit TM) whose rounds find a unit's read base by an LDS round trip
-// (slot base written by the read's start lane, read back by every lane) instead
-// of a scalar pass over the round's read starts: short reads (C1 / C2) start
-// several reads per round
-#ifndef MPC_LDS_BASE_MODES
-#define MPC_LDS_BASE_MODES 0x07
-#endif
 template <int TM> constexpr bool lds_base() { return (MPC_LDS_BASE_MODES >> TM) & 1; }
-__host__ __device__ constexpr bool lds_base_rt(int tm) { return (MPC_LDS_BASE_MODES >> tm) & 1; }
-
-template <int WIN, bool SV>              // SV: the read-base slots (lds_base modes)
-struct alignas(16) WaveLds {            // per-wave LDS of K_parse
-  int32_t s_val[SV ? kSlots : 0];       // read base: i = s_val + window prefix of advances
-  int32_t s_ts[kSlots];                 // tstart (clamped to [MPC_TSTART_MIN, kICap])
-  int32_t s_read[kSlots];               // local read index
-  int32_t s_iend[kSlots];               // i_end | bit 30: read has a downstream flank
-  int64_t s_end[kSlots];                // cs offset of the read's end
-  uint8_t stage[WIN + 16];              // window bytes (+16: word reads past the end)
-  uint8_t ra[WIN / 8];                  // read-start bits, bit = byte
-  uint16_t tok[tok_cap<WIN>() + 2 + 64];  // unit starts in [P, C), then the sentinel C; bits 12-14: ':' prefix
-                                        // operand length, bit 15: read start (+64: unconditional loads)
-};
 
 struct ParseArgs {  // slim argument block (no SGPR spills)
   const uint8_t* cs; const int64_t* cs_off; const int32_t* tstart;
@@ -420,42 +341,8 @@ struct ParseArgs {  // slim argument block (no SGPR spills)
   int32_t defer_off;  // deferred placement (K_parse DP): LDS byte offset of the per-wave event queues
 };
 
-// Substitution events (tally mode 3, references too long for LDS substitution
-// tallies): position within a kSubWin-position window << 2 | code, per wave and
-// window in the wave's region [(cs_off[ra] - cs_base) / kSubEvBytes + 2 ra, ...)
-// of window w's slice; K_subs tallies them per window in LDS.  A '*' token takes
-// at least 2 cs bytes ('*' and the base it writes, :96 -- minimap2 writes 3,
-// "*ag", but "*a" is valid: round 5 sized the regions by 3 bytes, which two-byte
-// tokens overran)
-constexpr int kSubWinBits = 14, kSubWin = 1 << kSubWinBits, kMaxSubWins = 4;
-constexpr int kSubEvBytes = 2;
-
-__host__ __device__ inline int parse_hl_words(int n) { return (n + 1 + 31) / 32; }
-// the chunk table (cs offset, read), the chunk counter and the page counter
-__host__ __device__ constexpr int parse_misc_bytes() { return (kMaxCh + 2) * 8 + (kMaxCh + 4) * 4 + 16; }
-static_assert(parse_misc_bytes() % 16 == 0 && kMaxCh % 4 == 0, "parse LDS misc area alignment");
-template <int WIN>
-// position tallies of K_parse: 0 = global atomics, 4 = global atomics AND the
-// LEFT bitmap / insertion-bucket counters / event-sort cursors in HBM (references
-// too long for any LDS mode, up to kMaxRefLen), 1 = LDS, 12 B per position
-// (sub 4 x u16, depth decrements | increments u16), 2 = LDS, 10 B per position
-// (the depth difference as one biased 16-bit half), 3 = depth differences in
-// LDS (2 B per position), substitutions global: references up to ~40 kb
-__host__ __device__ inline int parse_lds_bytes(int n_max, int tm, int nbmax, int nw) {
-  const int wl = lds_base_rt(tm) ? (int)sizeof(WaveLds<WIN, true>) : (int)sizeof(WaveLds<WIN, false>);
-  if (tm == 4) return nw * wl + parse_misc_bytes();  // per-gap state in HBM
-  const int tallies = tm == 0 ? 0 : tm == 1 ? 12 * (n_max + 1) : tm == 2 ? 8 * (n_max + 1) + 4 * ((n_max + 2) / 2)
-                                                                 : 4 * ((n_max + 2) / 2);
-  const int buckets = 16 * nbmax + 4;  // epilogue: counts, cursors, chunk counts, chunk offsets
-  return nw * wl + parse_misc_bytes() + 4 * parse_hl_words(n_max) + 4 * nbmax +
-         (tallies > buckets ? tallies : buckets);
-}
-
-// reads per parse workgroup that keep the 16-bit LDS tallies exact: a read adds
-// at most 2 to a position's depth counters; modes 2 / 3 keep the depth
-// difference as one half biased by 0x8000 (|sum| <= 2 * 16383 < 0x8000),
-// mode 1 keeps decrements and increments apart (2 * 32767 < 2^16)
-__host__ __device__ constexpr int64_t wg_reads_cap(int tm) { return tm == 2 || tm == 3 ? 16383 : 32767; }
+// (substitution events, the tally modes' LDS bytes and the reads-per-workgroup
+// cap of the 16-bit tallies: mpc_geometry.h)
 
 struct TokInfo { int adv; int kind; uint32_t pay; uint32_t err; };
 
@@ -1549,7 +1436,6 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
 // per (sample, window, chunk of <= kSubsWG parse workgroups); wave v walks the
 // chunk's regions v, v + 16, ... (8 loads in flight per lane).
 // ---------------------------------------------------------------------------
-constexpr int kSubsWG = 32;  // parse workgroups per K_subs block, at most
 // K_subs blocks store their 16-bit tallies in a slab row each, reduced per
 // (sample, window) by K_subsum (instead of every block adding its ~4 n counters
 // into the same words with global atomics)
@@ -1729,7 +1615,6 @@ constexpr int kGatherLds = 2048;  // source blocks whose prefix stays in LDS (en
 // the digit's cursor in the wave's own LDS row (no barrier inside the walk:
 // 4 per pass).  Force-inlined at call sites whose buffers are all LDS or all
 // HBM, so the accesses compile to ds_* / global_* instead of flat.
-constexpr int kRS = 1024;
 template <int U>  // chunks of 64 entries in flight per wave (HBM: latency; LDS: few)
 __device__ __forceinline__ void rsort_pass(const uint32_t* sk, const int32_t* sv, uint32_t* dk, int32_t* dv, int sh,
                                            int64_t s0, int64_t s1, int32_t (*wc)[256], int32_t* hb) {
@@ -2020,9 +1905,7 @@ __global__ __launch_bounds__(kRS) void K_rsort(Dev d, int32_t nblocks, int32_t e
 // to 64 reads).  A gap with more than 64 events, or few events overall, sends
 // the launch to K_rsort instead (path word rsflag[0]: 1 = this path).
 // ---------------------------------------------------------------------------
-constexpr int64_t kRsortMultiBlocks = 512;      // K_rsplit blocks (of 1024 reads) above which the plan takes this path
-constexpr int kScanPer = 8;                     // gaps per thread of K_rscan
-constexpr int kScanBlk = 1024 * kScanPer;       // gaps per K_rscan block
+// (kRsortMultiBlocks, kScanPer, kScanBlk: mpc_geometry.h)
 constexpr int kSegMax = 64;
 
 __global__ __launch_bounds__(1024) void K_rscan1(Dev d) {
@@ -2212,9 +2095,7 @@ __device__ __forceinline__ int64_t run_left(const int32_t* rs, const int32_t* rs
 // K_units cuts every entry's events into units of <= kUnit events (hot
 // buckets become many units) and appends them to one list.
 // ---------------------------------------------------------------------------
-constexpr int kUB = 1024;             // threads of K_ins and of K_left's default geometry
 constexpr int kLeftVals = 4096;       // mixed RIGHT reads of a bucket staged in K_left's LDS
-constexpr int kEPT = 16;         // events per thread per unit (loads batched)
 constexpr int kUnit = kUB * kEPT;     // events per work unit (K_left<kUB>; K_left<512>: half)
 
 struct UnitArgs {
@@ -2892,12 +2773,9 @@ __global__ __launch_bounds__(256) void K_wofold(Dev d) {
 // Within a run of LEFT events hi is constant, so only the run's longest LEFT
 // string matters (M); run k is closed by the gap's k-th mixed RIGHT event
 // (length runR).  One thread per gap replays its runs; the row counts and the
-// depth difference array are then scanned in the same launch (K_layout).
+// depth difference array are then scanned in the same launch (K_layout, kGB
+// gaps per block).
 // ---------------------------------------------------------------------------
-#ifndef MPC_LAYOUT_GAPS
-#define MPC_LAYOUT_GAPS 256
-#endif
-constexpr int kGB = MPC_LAYOUT_GAPS;  // gaps per K_layout block (fewer blocks: a shorter look-back chain)
 
 // K_layout = K_replay + K_assemble in ONE launch: the per-gap replay, then the
 // row offsets and depths as block scans chained across blocks by a decoupled
@@ -3572,8 +3450,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCR > 1 ? 4
   }
 }
 
-constexpr int kKB = 1024;  // rows per K_select block (4 per thread)
-
 // keep[row] = emitted (:428) and the ordered compaction of the kept calls in
 // ONE launch: every block publishes its kept count, then chains the counts of
 // the blocks before it by a decoupled look-back (one 64-bit status word per
@@ -3645,9 +3521,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void K
 }  // namespace
 
 // ===========================================================================
-// Host side: plan, workspace layout, phases, C-ABI
+// Host side: binding a plan (mpc_plan.h; planned by mpc_plan.cpp), launches, phases
 // ===========================================================================
-static thread_local std::string g_err;
 // look-back launch epochs (K_layout, K_select): one process-wide sequence, so a
 // status word another plan left in reused memory never carries a live tag; 0 is
 // never used (zeroed words)
@@ -3657,9 +3532,6 @@ static uint32_t next_epoch() {
   do v = (e.fetch_add(1) + 1) & 0x3fffffffu; while (v == 0);
   return v;
 }
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-// the library's other translation units (mpc_verify.hip) report through the same mpc_last_error()
-__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg) { return fail(code, msg); }
 
 #define HIPCHK(x)                                                                  \
   do {                                                                             \
@@ -3667,85 +3539,45 @@ __attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg) {
     if (e_ != hipSuccess) return fail(MPC_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-struct mpc_plan {
-  mpc_input in;
-  std::vector<int64_t> ref_len, read_begin;
-  std::vector<int32_t> h_n, h_gbase;
-  int64_t N = 0, Ng = 0, G = 0, row_cap = 0, runs_cap = 0, ins_cap = 0, ovf_cap = 0, pages_cap = 0;
-  int64_t wo_cap = 0, wo_p2 = 1;  // strings into wrapped odd positions (negative starts): list bound, sort size
-  int32_t S = 0;
-  int32_t overrides = 0;  // MPC_OVR_* (experiment builds only)
-  uint32_t sentinel = 0;
-  int end_bit = 0;
-  bool rsort_multi = false;  // mixed RIGHT events sorted by K_rscan / K_rscatter / K_rsegsort (many reads)
-  size_t ws_bytes = 0;
-  uint8_t* ws = nullptr;
-  std::vector<int32_t> work_parse, work_bc, work_sub;  // int4 records
-  std::vector<int32_t> work_subsum;                   // int4 {sample, window, first K_subs block, end}
-  int subsum_rows = 0;                                // most K_subs blocks of one (sample, window)
-  std::vector<int32_t> work_wave;                     // per parse workgroup: kMaxPW + 1 wave boundaries
-  int32_t sub_wins = 0;                               // tally mode 3: substitution-event windows
-  int64_t subev_cap = 0;
-  int n_parse_wg = 0, parse_lds = 0, nbmax = 1, parse_win = 1024, parse_nw = 8;
-  int defer_off = 0;                                  // K_parse deferred placement: its queues' LDS offset (0: off)
-  int64_t n_bc = 0, units_cap = 0, max_wg_reads = 0;
-  int32_t left_ub = 1024;  // K_left threads per block
-  int32_t shard = 0, n_shards = 1;
-  int tally_mode = 0;  // K_parse TM
-  enum {
-    B_STATUS, B_NOF, B_GBASE, B_IEND, B_PGOWN, B_INSSORT, B_BKCNT, B_BKOFF, B_RBASE, B_OVF, B_OVFCNT,
-    B_HASLEFT, B_KIN, B_VIN, B_KOUT, B_VOUT, B_KTMP, B_VTMP, B_BCNT, B_BPRE, B_RLEN, B_RPOS, B_RSTART, B_RSLOC, B_ROFF, B_RCNT, B_RCNTALL,
-    // MAXR, M, RUNR adjacent and in this order: one MAX exchange over their span (mpc.h)
-    B_DIFF, B_SUB, B_MAXR, B_M, B_RUNR, B_HIR, B_LOR, B_LOF, B_ROWCNT, B_ROWBASE, B_BSUM, B_ROWS,
-    B_META, B_RES, B_KEEP, B_KSUM, B_CALLS, B_NCALLS, B_MAXD, B_SROW, B_WPARSE, B_WBC, B_UNITS, B_RUNT,
-    B_SUBEV, B_SUBCNT, B_WSUB, B_BKCUR, B_WWAVE, B_SUBSLAB, B_WSUBSUM, B_GCNT, B_KSLOT, B_RSFLAG, B_PGLIST,
-    B_WOEV, B_WOKEY, B_WOIDX, B_WOERUN, B_WOPOS, B_WORUN, B_WOREC, B_WOALL, B_WOCOV, B_COUNT
-  };
-  size_t off[B_COUNT];
-  size_t sz[B_COUNT];
-  int64_t cnt[B_COUNT];
-  bool bound = false;
-  bool runt_dirty = true;  // runt may hold tallies: K_clear zeroes it (K_ins zeroes what it maps)
-  Dev dev() const;
-};
-
-
 template <class T>
 static T* at(const mpc_plan* p, int b) { return reinterpret_cast<T*>(p->ws + p->off[b]); }
 
-Dev mpc_plan::dev() const {
+// the device-side views of a bound plan
+static Dev plan_dev(const mpc_plan* p) {
+  using P = mpc_plan;
+  const mpc_input& in = p->in;
   Dev d{};
   d.ref = in.ref; d.ref_off = in.ref_off; d.cs = in.cs; d.cs_off = in.cs_off; d.tstart = in.tstart;
   d.up = in.up; d.up_off = in.up_off; d.down = in.down; d.down_off = in.down_off; d.sample = in.sample;
-  d.N = N; d.Ng = Ng; d.read_offset = in.read_offset; d.cs_base = in.cs_base; d.S = S; d.G = (int32_t)G;
-  d.n_of = at<int32_t>(this, B_NOF); d.gbase = at<int32_t>(this, B_GBASE);
-  d.status = at<uint32_t>(this, B_STATUS); d.i_end = at<int32_t>(this, B_IEND);
-  d.ovf = at<Ovf>(this, B_OVF); d.ovf_cnt = at<uint32_t>(this, B_OVFCNT); d.ovf_cap = ovf_cap;
-  d.hasleft = at<uint32_t>(this, B_HASLEFT); d.maxR = at<int32_t>(this, B_MAXR);
-  d.keys_in = at<uint32_t>(this, B_KIN); d.vals_in = at<int32_t>(this, B_VIN);
-  d.keys_out = at<uint32_t>(this, B_KOUT); d.vals_out = at<int32_t>(this, B_VOUT);
-  d.keys_tmp = at<uint32_t>(this, B_KTMP); d.vals_tmp = at<int32_t>(this, B_VTMP);
-  d.bcnt = at<int32_t>(this, B_BCNT); d.bpre = at<int32_t>(this, B_BPRE);
-  d.gcnt = rsort_multi ? at<int32_t>(this, B_GCNT) : nullptr;
-  d.kslot = rsort_multi ? at<int32_t>(this, B_KSLOT) : nullptr;
-  d.rsflag = rsort_multi ? at<int32_t>(this, B_RSFLAG) : nullptr;
-  d.rlen = at<int32_t>(this, B_RLEN); d.rpos = at<int32_t>(this, B_RPOS); d.right_start = at<int32_t>(this, B_RSTART);
-  d.rsl = at<int32_t>(this, B_RSLOC); d.roff = at<int32_t>(this, B_ROFF); d.rcnt = at<int32_t>(this, B_RCNT);
-  d.rcnt_all = at<int32_t>(this, B_RCNTALL); d.shard = shard; d.n_shards = n_shards;
-  d.diff = at<int32_t>(this, B_DIFF); d.sub = at<uint32_t>(this, B_SUB);
-  d.M = at<int32_t>(this, B_M); d.runR = at<int32_t>(this, B_RUNR); d.runt = at<uint32_t>(this, B_RUNT);
-  d.hiR = at<int32_t>(this, B_HIR); d.loR = at<int32_t>(this, B_LOR);
-  d.lo_f = at<int32_t>(this, B_LOF); d.rowcnt = at<int32_t>(this, B_ROWCNT); d.row_base = at<int32_t>(this, B_ROWBASE);
-  d.bsum = at<int32_t>(this, B_BSUM);
-  d.rows = at<uint32_t>(this, B_ROWS); d.meta = at<uint8_t>(this, B_META);
-  d.row_cap = row_cap;
-  d.res = at<uint32_t>(this, B_RES); d.keep = at<int32_t>(this, B_KEEP); d.ksum = at<int32_t>(this, B_KSUM);
-  d.calls = at<uint32_t>(this, B_CALLS); d.ncalls = at<int32_t>(this, B_NCALLS); d.maxdepth = at<uint32_t>(this, B_MAXD);
-  d.srow = at<int32_t>(this, B_SROW);
-  d.wo = at<WoEv>(this, B_WOEV); d.wo_key = at<uint64_t>(this, B_WOKEY); d.wo_idx = at<uint32_t>(this, B_WOIDX);
-  d.wo_erun = at<int32_t>(this, B_WOERUN); d.wo_pos = at<WoPos>(this, B_WOPOS); d.wo_run = at<WoRun>(this, B_WORUN);
-  d.wo_cap = wo_cap;
-  if (n_shards > 1 && wo_cap > 0) d.wo_x = at<uint8_t>(this, B_WOREC);  // (B_WOALL, B_WOCOV follow: wo_all(), wo_cov())
+  d.N = p->N; d.Ng = p->Ng; d.read_offset = in.read_offset; d.cs_base = in.cs_base; d.S = p->S; d.G = (int32_t)p->G;
+  d.n_of = at<int32_t>(p, P::B_NOF); d.gbase = at<int32_t>(p, P::B_GBASE);
+  d.status = at<uint32_t>(p, P::B_STATUS); d.i_end = at<int32_t>(p, P::B_IEND);
+  d.ovf = at<Ovf>(p, P::B_OVF); d.ovf_cnt = at<uint32_t>(p, P::B_OVFCNT); d.ovf_cap = p->ovf_cap;
+  d.hasleft = at<uint32_t>(p, P::B_HASLEFT); d.maxR = at<int32_t>(p, P::B_MAXR);
+  d.keys_in = at<uint32_t>(p, P::B_KIN); d.vals_in = at<int32_t>(p, P::B_VIN);
+  d.keys_out = at<uint32_t>(p, P::B_KOUT); d.vals_out = at<int32_t>(p, P::B_VOUT);
+  d.keys_tmp = at<uint32_t>(p, P::B_KTMP); d.vals_tmp = at<int32_t>(p, P::B_VTMP);
+  d.bcnt = at<int32_t>(p, P::B_BCNT); d.bpre = at<int32_t>(p, P::B_BPRE);
+  d.gcnt = p->rsort_multi ? at<int32_t>(p, P::B_GCNT) : nullptr;
+  d.kslot = p->rsort_multi ? at<int32_t>(p, P::B_KSLOT) : nullptr;
+  d.rsflag = p->rsort_multi ? at<int32_t>(p, P::B_RSFLAG) : nullptr;
+  d.rlen = at<int32_t>(p, P::B_RLEN); d.rpos = at<int32_t>(p, P::B_RPOS); d.right_start = at<int32_t>(p, P::B_RSTART);
+  d.rsl = at<int32_t>(p, P::B_RSLOC); d.roff = at<int32_t>(p, P::B_ROFF); d.rcnt = at<int32_t>(p, P::B_RCNT);
+  d.rcnt_all = at<int32_t>(p, P::B_RCNTALL); d.shard = p->shard; d.n_shards = p->n_shards;
+  d.diff = at<int32_t>(p, P::B_DIFF); d.sub = at<uint32_t>(p, P::B_SUB);
+  d.M = at<int32_t>(p, P::B_M); d.runR = at<int32_t>(p, P::B_RUNR); d.runt = at<uint32_t>(p, P::B_RUNT);
+  d.hiR = at<int32_t>(p, P::B_HIR); d.loR = at<int32_t>(p, P::B_LOR);
+  d.lo_f = at<int32_t>(p, P::B_LOF); d.rowcnt = at<int32_t>(p, P::B_ROWCNT); d.row_base = at<int32_t>(p, P::B_ROWBASE);
+  d.bsum = at<int32_t>(p, P::B_BSUM);
+  d.rows = at<uint32_t>(p, P::B_ROWS); d.meta = at<uint8_t>(p, P::B_META);
+  d.row_cap = p->row_cap;
+  d.res = at<uint32_t>(p, P::B_RES); d.keep = at<int32_t>(p, P::B_KEEP); d.ksum = at<int32_t>(p, P::B_KSUM);
+  d.calls = at<uint32_t>(p, P::B_CALLS); d.ncalls = at<int32_t>(p, P::B_NCALLS); d.maxdepth = at<uint32_t>(p, P::B_MAXD);
+  d.srow = at<int32_t>(p, P::B_SROW);
+  d.wo = at<WoEv>(p, P::B_WOEV); d.wo_key = at<uint64_t>(p, P::B_WOKEY); d.wo_idx = at<uint32_t>(p, P::B_WOIDX);
+  d.wo_erun = at<int32_t>(p, P::B_WOERUN); d.wo_pos = at<WoPos>(p, P::B_WOPOS); d.wo_run = at<WoRun>(p, P::B_WORUN);
+  d.wo_cap = p->wo_cap;
+  if (p->n_shards > 1 && p->wo_cap > 0) d.wo_x = at<uint8_t>(p, P::B_WOREC);  // (B_WOALL, B_WOCOV follow: wo_all(), wo_cov())
   return d;
 }
 
@@ -3926,426 +3758,7 @@ static inline unsigned nblk(int64_t n, int b = 256) {
 
 extern "C" {
 
-int mpc_version(void) { return MPC_ABI_VERSION; }
-
 int mpc_build_flags(void) { return MPC_BF_STAMPS_ | MPC_BF_TUNING_ | MPC_BF_VARIANT_; }
-
-size_t mpc_input_layout(size_t* off, int cap) {
-#define MPC_F(f) offsetof(mpc_input, f)
-  static const size_t o[] = {MPC_F(ref), MPC_F(ref_off), MPC_F(cs), MPC_F(cs_off), MPC_F(tstart), MPC_F(up),
-                             MPC_F(up_off), MPC_F(down), MPC_F(down_off), MPC_F(sample), MPC_F(n_samples),
-                             MPC_F(h_ref_len), MPC_F(h_read_begin), MPC_F(n_reads), MPC_F(cs_bytes), MPC_F(cs_base),
-                             MPC_F(read_offset), MPC_F(n_reads_global), MPC_F(shard), MPC_F(n_shards),
-                             MPC_F(h_cs_off), MPC_F(parse_cus), MPC_F(neg_reads), MPC_F(neg_cs_bytes)};
-#undef MPC_F
-  static_assert(sizeof(o) / sizeof(o[0]) == MPC_INPUT_FIELDS, "mpc_input field table");
-  for (int k = 0; off && k < cap && k < MPC_INPUT_FIELDS; ++k) off[k] = o[k];
-  return sizeof(mpc_input);
-}
-const char* mpc_last_error(void) { return g_err.c_str(); }
-
-int mpc_plan_create(const mpc_input* in, int64_t row_cap, mpc_plan** out) {
-  if (!in || !out) return fail(MPC_E_ARG, "null argument");
-  if (in->n_samples <= 0) return fail(MPC_E_ARG, "n_samples must be > 0");
-  auto* p = new mpc_plan();
-  p->in = *in;
-  p->S = in->n_samples;
-  p->N = in->n_reads;
-  p->Ng = in->n_reads_global > 0 ? in->n_reads_global : in->n_reads;
-  p->n_shards = in->n_shards > 0 ? in->n_shards : 1;
-  p->shard = in->shard;
-  if (p->shard < 0 || p->shard >= p->n_shards) { delete p; return fail(MPC_E_ARG, "shard out of range"); }
-  if (p->Ng < p->N || in->read_offset < 0 || in->read_offset + p->N > p->Ng) {
-    delete p;
-    return fail(MPC_E_ARG, "read shard [read_offset, read_offset + n_reads) outside [0, n_reads_global)");
-  }
-  p->ref_len.assign(in->h_ref_len, in->h_ref_len + p->S);
-  p->read_begin.assign(in->h_read_begin, in->h_read_begin + p->S + 1);
-  p->h_n.resize(p->S);
-  p->h_gbase.resize(p->S + 1);
-  int64_t g = 0;
-  for (int s = 0; s < p->S; ++s) {
-    if (p->ref_len[s] < 0 || p->ref_len[s] > kMaxRefLen) { delete p; return fail(MPC_E_ARG, "reference length out of range (at most 2^22 - 2 bases)"); }
-    p->h_n[s] = (int32_t)p->ref_len[s];
-    p->h_gbase[s] = (int32_t)g;
-    g += p->ref_len[s] + 1;
-  }
-  p->h_gbase[p->S] = (int32_t)g;
-  p->G = g;
-  if (p->G >= (1ll << 30)) { delete p; return fail(MPC_E_ARG, "too many positions"); }
-  if (p->Ng >= (1ll << 30)) { delete p; return fail(MPC_E_ARG, "too many reads (event words hold 30-bit read indices)"); }
-  p->row_cap = row_cap > 0 ? row_cap : 1;
-  if (p->row_cap >= (1ll << 31)) { delete p; return fail(MPC_E_ARG, "row capacity must be < 2^31"); }
-  p->runs_cap = p->Ng + p->G;
-  p->ins_cap = in->cs_bytes / 2 + 3 * p->N + 16;  // insertions (>= 2 cs bytes each) + slack per read
-  p->ovf_cap = in->cs_bytes / 6 + 16;
-  // strings Python's negative wrap writes into odd positions: <= 2 flanks per
-  // read with a negative start plus its '+' insertions (>= 2 cs bytes each);
-  // one shard only (the replay needs every string of a position)
-  if (in->neg_reads < 0 || in->neg_cs_bytes < 0) { delete p; return fail(MPC_E_ARG, "negative neg_reads / neg_cs_bytes"); }
-  // (several shards: neg_reads / neg_cs_bytes are the totals over all of them, so every shard
-  // sizes the same list and holds all shards' strings after the gather)
-  p->wo_cap = in->neg_reads > 0 ? std::min<int64_t>(kWoCapMax, 2 * in->neg_reads + in->neg_cs_bytes / 2 + 16) : 0;
-  while (p->wo_p2 < p->wo_cap) p->wo_p2 <<= 1;
-  int eb = 1;
-  while ((1ll << eb) <= p->G + 1) ++eb;
-  p->end_bit = eb;
-  p->sentinel = (uint32_t)((1ull << eb) - 1);
-  // ---- work tables ----
-  {
-    int64_t n_max = 0;
-    for (int s = 0; s < p->S; ++s) {
-      n_max = std::max<int64_t>(n_max, p->ref_len[s]);
-      p->nbmax = std::max<int>(p->nbmax, (int)((p->ref_len[s] + 1 + kBW - 1) / kBW));
-    }
-    // parse geometry: tally mode, window and waves per workgroup that give the
-    // most resident waves per CU (ties: the earlier candidate -- LDS tallies,
-    // larger windows, the 12-byte tallies)
-    const int lds_cap = 160 * 1024;
-    const int max_waves_cu = 16;  // VGPR budget of K_parse (<= 128 VGPRs -> 4 waves per SIMD)
-    auto lds_of = [&](int win, int tm, int nw) {
-      return win == 512    ? parse_lds_bytes<512>((int)n_max, tm, p->nbmax, nw)
-             : win == 2048 ? parse_lds_bytes<2048>((int)n_max, tm, p->nbmax, nw)
-                           : parse_lds_bytes<1024>((int)n_max, tm, p->nbmax, nw);
-    };
-    // score = resident waves x window efficiency (measured at C2: 512 B windows
-    // cost ~25 % more per byte than 2 KiB ones, 1 KiB ~5 %).  Tally mode 3 keeps
-    // only depth in LDS; its substitutions are window events (K_subs) while the
-    // reference fits kMaxSubWins windows, and then it competes on score: at C3 /
-    // C4 (10 kb) its 16 waves beat tm 2's 12 (parse 3060 -> 2947 us, 3396 ->
-    // 3004 us), at C2 tm 1 with 16 waves wins the tie (167 vs 197 us).  Beyond
-    // that its substitutions are global atomics: only when tm 1 / 2 do not fit.
-    const bool sub_events = n_max <= (int64_t)kSubWin * kMaxSubWins;
-    static const int cand[10][2] = {{1, 2048}, {2, 2048}, {1, 1024}, {2, 1024}, {3, 2048}, {3, 1024},
-                                    {1, 512}, {0, 2048}, {0, 1024}, {0, 512}};
-    int best = -1, per_cu = 1;
-    // tuning override for measurements: MPC_PARSE_GEOMETRY="tm,win,nw" takes that
-    // candidate when it fits the LDS budget (else the planner's choice)
-    int o_tm = -1, o_win = -1, o_nw = -1;
-#ifdef MPC_TUNING_OVERRIDES  // experiment builds only (scripts/geom_ab.py); reported in mpc_plan_info.overrides
-    if (const char* e = getenv("MPC_PARSE_GEOMETRY")) sscanf(e, "%d,%d,%d", &o_tm, &o_win, &o_nw);
-#endif
-    for (const auto& c : cand)
-      for (int nw : {16, 12, 8}) {
-        if (c[0] == 3 && !sub_events && best > 0) break;  // global-atomic tm 3 only when nothing else fits
-        if (c[0] == 0 && best > 0) break;                  // tm 0 only when no LDS mode fits
-        const int lds = lds_of(c[1], c[0], nw);
-        if (lds > lds_cap) continue;
-        const int wgs = std::max(1, std::min(lds_cap / lds, max_waves_cu / nw));
-        int score = wgs * nw * (c[1] == 512 ? 75 : c[1] == 1024 ? 95 : 100);
-        const bool forced = c[0] == o_tm && c[1] == o_win && nw == o_nw;
-        if (forced) score = 1 << 30;
-        if (score > best) {
-          best = score; p->tally_mode = c[0]; p->parse_win = c[1]; p->parse_nw = nw; per_cu = wgs;
-          p->overrides = forced ? (p->overrides | MPC_OVR_GEOMETRY) : (p->overrides & ~MPC_OVR_GEOMETRY);
-        }
-      }
-    if (best < 0) {
-      // references beyond every LDS mode (~312 kb): per-gap parse state in HBM
-      for (int nw : {16, 12, 8}) {
-        const int lds = parse_lds_bytes<1024>((int)n_max, 4, p->nbmax, nw);
-        if (lds > lds_cap) continue;
-        const int wgs = std::max(1, std::min(lds_cap / lds, max_waves_cu / nw));
-        if (wgs * nw > best) { best = wgs * nw; p->tally_mode = 4; p->parse_win = 1024; p->parse_nw = nw; per_cu = wgs; }
-      }
-    }
-    if (best < 0) { delete p; return fail(MPC_E_ARG, "reference too long for the LDS budget"); }
-    p->parse_lds = lds_of(p->parse_win, p->tally_mode, p->parse_nw);
-    // workgroups per sample: the smallest largest-chunk R with sum_s ceil(ns / R)
-    // <= the resident slots (256 CUs x per_cu), so that the parse is one balanced
-    // wave of workgroups (C5: 24 samples x 10 instead of x 11 = 264 > 256 slots,
-    // whose 8 second-wave workgroups doubled K_parse); >= 64 reads per workgroup
-    const int cus = in->parse_cus > 0 && in->parse_cus < 256 ? in->parse_cus : 256;
-    int64_t target = (int64_t)cus * per_cu;
-#ifdef MPC_TUNING_OVERRIDES
-    if (const char* e = getenv("MPC_PARSE_WGS")) {  // measurement override
-      target = std::max<int64_t>(1, atoll(e));
-      p->overrides |= MPC_OVR_WGS;
-    }
-#endif
-    const int64_t wcap = wg_reads_cap(p->tally_mode);
-    auto chunks = [&](int64_t ns, int64_t R) {
-      int64_t ch = (ns + R - 1) / R;
-      ch = std::min<int64_t>(ch, (ns + 63) / 64);
-      return std::max<int64_t>(ch, (ns + wcap - 1) / wcap);
-    };
-    int64_t R_lo = 1, R_hi = std::max<int64_t>(p->N, 1);
-    while (R_lo < R_hi) {
-      const int64_t mid = (R_lo + R_hi) / 2;
-      int64_t tot = 0;
-      for (int s = 0; s < p->S; ++s) tot += chunks(p->read_begin[s + 1] - p->read_begin[s], mid);
-      if (tot <= target) R_hi = mid; else R_lo = mid + 1;
-    }
-    // boundaries of [a, b) cut into k parts: equal cs BYTES when the host copy
-    // of cs_off is given (the parse time of a read range follows its bytes, not
-    // its read count: a count split left waves idle at the epilogue barrier 22 %
-    // of their time, profiles/r03_stamps), else equal read counts
-    const int64_t* hco = in->h_cs_off;
-    auto cut = [&](int64_t a, int64_t b, int64_t k, std::vector<int64_t>& out) {
-      out.assign((size_t)k + 1, a);
-      out[(size_t)k] = b;
-      for (int64_t c = 1; c < k; ++c) {
-        int64_t x = a + (b - a) * c / k;
-        if (hco) {
-          const int64_t tgt = hco[a] + (hco[b] - hco[a]) * c / k;
-          x = std::lower_bound(hco + a, hco + b + 1, tgt) - hco;
-        }
-        out[(size_t)c] = std::min(std::max(x, out[(size_t)c - 1]), b);
-      }
-    };
-    std::vector<int64_t> bnd;
-    std::vector<int> pw_begin(p->S + 1, 0);
-    for (int s = 0; s < p->S; ++s) {
-      pw_begin[s] = (int)(p->work_parse.size() / 4);
-      const int64_t a = p->read_begin[s], b = p->read_begin[s + 1], ns = b - a;
-      if (ns <= 0) continue;
-      const int64_t ch = chunks(ns, R_lo);
-      cut(a, b, ch, bnd);
-      bool capped = true;  // the byte split must keep the 16-bit tallies' reads-per-workgroup cap
-      for (int64_t c = 0; c < ch; ++c) capped &= bnd[(size_t)c + 1] - bnd[(size_t)c] <= wcap;
-      for (int64_t c = 0; c < ch; ++c) {
-        const int64_t x = capped ? bnd[(size_t)c] : a + ns * c / ch;
-        const int64_t y = capped ? bnd[(size_t)c + 1] : a + ns * (c + 1) / ch;
-        if (y > x) p->work_parse.insert(p->work_parse.end(), {s, (int32_t)x, (int32_t)y, 0});
-        p->max_wg_reads = std::max<int64_t>(p->max_wg_reads, y - x);
-      }
-    }
-    // the chunks of every workgroup (its waves take them in turn): nw chunks
-    // with 5/8 of the bytes, then nw with a quarter and nw with the last
-    // eighth, so the last chunks taken are the small ones (measured against 4
-    // groups of 1/2..1/8, 2 groups, equal quarters and one chunk per wave:
-    // DESIGN.md "Parse work split")
-    {
-      constexpr int kGroups = 3;
-      const int nw = p->parse_nw, nch = std::min(kMaxCh, kGroups * nw);
-      std::vector<int64_t> part;
-      for (size_t k = 0; k < p->work_parse.size(); k += 4) {
-        const int64_t a = p->work_parse[k + 1], b = p->work_parse[k + 2];
-        std::vector<int64_t> cb{a};
-        static constexpr double grp[kGroups] = {0.625, 0.25, 0.125};
-        // groups only while the smallest chunks still hold about half a window
-        // (else one chunk per wave: C1's 3 KiB per wave ran 11 % slower cut in three)
-        const int64_t wg_bytes = hco ? hco[b] - hco[a] : (b - a) * (in->cs_bytes / std::max<int64_t>(1, p->N));
-        const int ng = wg_bytes >= 4 * (int64_t)nw * p->parse_win ? kGroups : 1;
-        int64_t lo = a;
-        double acc = 0;
-        for (int g = 0; g < ng && (int)cb.size() - 1 < nch; ++g) {
-          acc += grp[g];
-          int64_t hi = b;
-          if (g < ng - 1) {  // group end: the read where the cumulative byte fraction is reached
-            if (hco) hi = std::lower_bound(hco + a, hco + b + 1, hco[a] + (int64_t)((hco[b] - hco[a]) * acc)) - hco;
-            else hi = a + (int64_t)((b - a) * acc);
-            hi = std::min(std::max(hi, lo), b);
-          }
-          cut(lo, hi, nw, part);
-          for (int c = 1; c <= nw; ++c) cb.push_back(part[(size_t)c]);
-          lo = hi;
-        }
-        p->work_parse[k + 3] = (int32_t)(cb.size() - 1);
-        for (int c = 0; c <= kMaxCh; ++c) p->work_wave.push_back((int32_t)cb[(size_t)std::min<int>(c, (int)cb.size() - 1)]);
-      }
-    }
-    pw_begin[p->S] = (int)(p->work_parse.size() / 4);
-    p->n_parse_wg = pw_begin[p->S];
-    // tally mode 3: substitutions as events per kSubWin-position window (K_subs)
-    p->sub_wins = 0;
-    if (p->tally_mode == 3 && sub_events) {
-      p->sub_wins = (int32_t)((n_max + kSubWin - 1) / kSubWin);
-      // parse workgroups per K_subs block: about one block per CU (each block's
-      // LDS tally is 128 KiB; more blocks = more flush atomics, fewer = fewer CUs)
-      int64_t pairs = 0;
-      for (int s = 0; s < p->S; ++s)
-        pairs += ((p->ref_len[s] + kSubWin - 1) / kSubWin) * (int64_t)(pw_begin[s + 1] - pw_begin[s]);
-      const int kc = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)kSubsWG, (pairs + 255) / 256,
-                                                                   65535 / std::max<int64_t>(1, p->max_wg_reads)}));
-      for (int s = 0; s < p->S; ++s)
-        for (int w = 0; w * (int64_t)kSubWin < p->ref_len[s]; ++w) {
-          const int b0 = (int)(p->work_sub.size() / 4);
-          for (int c = pw_begin[s]; c < pw_begin[s + 1]; c += kc)
-            p->work_sub.insert(p->work_sub.end(), {s, w, c, std::min(c + kc, pw_begin[s + 1])});
-          const int b1 = (int)(p->work_sub.size() / 4);
-          if (b1 > b0) p->work_subsum.insert(p->work_subsum.end(), {s, w, b0, b1});
-          p->subsum_rows = std::max(p->subsum_rows, b1 - b0);
-        }
-    }
-    // deferred placement: the per-wave queues after the parse LDS, when they fit
-    p->defer_off = 0;
-    if (p->parse_win == 2048 && p->in.neg_reads == 0 &&
-        (p->tally_mode == 1 || (p->tally_mode == 3 && p->sub_wins == 1))) {
-      const int off = (p->parse_lds + 15) & ~15;
-      const int end = off + defer_bytes(p->parse_nw);
-      if (end <= lds_cap && std::max(1, std::min(lds_cap / end, max_waves_cu / p->parse_nw)) == per_cu) {
-        p->defer_off = off;
-        p->parse_lds = end;
-      }
-    }
-    for (int s = 0; s < p->S; ++s) {
-      const int nb = (int)((p->ref_len[s] + 1 + kBW - 1) / kBW);
-      if (pw_begin[s + 1] == pw_begin[s]) continue;  // no reads: nothing to tally
-      for (int b = 0; b < nb; ++b)  // insertion buckets
-        for (int c = pw_begin[s]; c < pw_begin[s + 1]; c += 256)
-          p->work_bc.insert(p->work_bc.end(), {s, b, c, std::min(c + 256, pw_begin[s + 1])});
-    }
-    p->n_bc = (int64_t)(p->work_bc.size() / 4);
-    // K_left blocks of 512 threads (units of 8 k events) when there are many
-    // small insertion buckets: C5's 24 x 469 buckets of ~3 k events each are
-    // ~22 units per block in turn, whose fixed per-unit cost dominated at 1024
-    // threads (K_left 352 -> 287 us).  Few or large buckets (C1-C4) keep 1024
-    // (measured 4-45 % slower at 512: one unit per block, latency-bound).  The
-    // bucket size is estimated from the cs bytes per (sample, bucket)
-    {
-      int64_t nb_all = 0;
-      for (int s = 0; s < p->S; ++s) nb_all += (p->ref_len[s] + 1 + kBW - 1) / kBW;
-      p->left_ub = nb_all > 4 * 512 && in->cs_bytes / nb_all < (256 << 10) ? 512 : kUB;
-    }
-    // work units of left_ub * kEPT / 64 pages (parse_page_base bounds the pages)
-    p->units_cap = (parse_page_base(in->cs_bytes, p->N, p->n_parse_wg, p->nbmax) + 1) / (p->left_ub * kEPT / kPgEv) +
-                   p->n_bc + 1;
-  }
-  const int64_t N = p->N, Ng = p->Ng, G = p->G, R = p->row_cap, RU = p->runs_cap;
-  const int64_t nbg = (G + kGB - 1) / kGB, nbk = (R + kKB - 1) / kKB;
-  auto set = [&](int b, int64_t count, size_t elem) { p->cnt[b] = count; p->sz[b] = (size_t)std::max<int64_t>(count, 1) * elem; };
-  set(mpc_plan::B_STATUS, MPC_ST_WORDS, 4);
-  set(mpc_plan::B_NOF, p->S, 4);
-  set(mpc_plan::B_GBASE, p->S + 1, 4);
-  set(mpc_plan::B_IEND, N, 4);
-  // insertion events in 64-event pages per (parse workgroup, bucket)
-  // (parse_page_base: the last workgroup's region ends at this bound)
-  p->pages_cap = parse_page_base(in->cs_bytes, N, p->n_parse_wg, p->nbmax) + 1;
-  set(mpc_plan::B_PGOWN, p->pages_cap, 4);
-  set(mpc_plan::B_PGLIST, p->pages_cap, 4);
-  set(mpc_plan::B_INSSORT, p->pages_cap * kPgEv, 4);
-  set(mpc_plan::B_BKCNT, (int64_t)p->n_parse_wg * p->nbmax, 4);
-  set(mpc_plan::B_BKOFF, (int64_t)p->n_parse_wg * p->nbmax, 4);
-  set(mpc_plan::B_RBASE, p->n_parse_wg, 8);
-  set(mpc_plan::B_OVF, p->ovf_cap, sizeof(Ovf));
-  set(mpc_plan::B_OVFCNT, 1, 4);
-  set(mpc_plan::B_HASLEFT, (G + 31) / 32 + 1, 4);
-  set(mpc_plan::B_MAXR, G, 4);
-  const int64_t nrb = (N + kRS - 1) / kRS;
-  set(mpc_plan::B_KIN, N, 4);
-  set(mpc_plan::B_VIN, N, 4);
-  set(mpc_plan::B_KOUT, N, 4);
-  set(mpc_plan::B_VOUT, N, 4);
-  set(mpc_plan::B_KTMP, N, 4);
-  set(mpc_plan::B_VTMP, N, 4);
-  set(mpc_plan::B_BCNT, nrb + 1, 4);
-  set(mpc_plan::B_BPRE, nrb + 1, 4);
-  // K_rsort's one workgroup gathers and sorts in time that grows with the read
-  // blocks (C3, 977 blocks: 88 us): many reads take the multi-workgroup path
-  p->rsort_multi = nrb > kRsortMultiBlocks;
-  set(mpc_plan::B_GCNT, p->rsort_multi ? G + 1 : 0, 4);
-  set(mpc_plan::B_KSLOT, p->rsort_multi ? nrb * (int64_t)kRS : 0, 4);
-  set(mpc_plan::B_RSFLAG, p->rsort_multi ? 4 + 2 * ((G + 1 + kScanBlk - 1) / kScanBlk) : 0, 4);
-  set(mpc_plan::B_RLEN, Ng, 4);
-  set(mpc_plan::B_RPOS, N > 0 ? N : 1, 4);
-  set(mpc_plan::B_RSTART, G + 1, 4);
-  set(mpc_plan::B_RSLOC, G + 1, 4);
-  set(mpc_plan::B_ROFF, G + 1, 4);
-  set(mpc_plan::B_RCNT, G, 4);
-  set(mpc_plan::B_RCNTALL, G * p->n_shards, 4);
-  set(mpc_plan::B_DIFF, G, 4);
-  set(mpc_plan::B_SUB, G * 4, 4);
-  set(mpc_plan::B_M, RU, 4);
-  set(mpc_plan::B_RUNR, RU, 4);
-  set(mpc_plan::B_HIR, RU, 4);
-  set(mpc_plan::B_LOR, RU, 4);
-  set(mpc_plan::B_LOF, G, 4);
-  set(mpc_plan::B_ROWCNT, G, 4);
-  set(mpc_plan::B_ROWBASE, G, 4);
-  set(mpc_plan::B_BSUM, 2 * nbg, 8);  // K_layout's look-back status words (rows, diff) per block
-  set(mpc_plan::B_ROWS, R * 4, 4);
-  set(mpc_plan::B_META, (R + 3) / 4 * 4, 1);
-  set(mpc_plan::B_RES, R * 4, 4);
-  set(mpc_plan::B_KEEP, nbk * 256, 4);
-  set(mpc_plan::B_KSUM, nbk, 8);  // K_select's per-block look-back status words
-  set(mpc_plan::B_CALLS, R * 4, 4);
-  set(mpc_plan::B_NCALLS, p->S + 1, 4);
-  set(mpc_plan::B_MAXD, p->S, 4);
-  set(mpc_plan::B_SROW, p->S, 4);
-  set(mpc_plan::B_WPARSE, (int64_t)p->work_parse.size(), 4);
-  set(mpc_plan::B_WBC, (int64_t)p->work_bc.size(), 4);
-  set(mpc_plan::B_UNITS, p->units_cap * 8, 4);  // 2 int4 per unit
-  set(mpc_plan::B_RUNT, RU * 16, 4);            // per run: inline LEFT bases [bi from the 3' end][code]
-  p->subev_cap = p->sub_wins ? in->cs_bytes / kSubEvBytes + 2 * N + 16 : 0;
-  set(mpc_plan::B_SUBEV, p->subev_cap * p->sub_wins, 2);
-  set(mpc_plan::B_SUBCNT, p->sub_wins ? (int64_t)p->n_parse_wg * kMaxCh * kMaxSubWins : 0, 4);
-  set(mpc_plan::B_WSUB, (int64_t)p->work_sub.size(), 4);
-  set(mpc_plan::B_BKCUR, p->tally_mode == 4 ? (int64_t)p->n_parse_wg * p->nbmax : 0, 4);
-  set(mpc_plan::B_WWAVE, (int64_t)p->work_wave.size(), 4);
-  set(mpc_plan::B_SUBSLAB, (int64_t)(p->work_sub.size() / 4) * kSubWin * 2, 4);
-  set(mpc_plan::B_WSUBSUM, (int64_t)p->work_subsum.size(), 4);
-  set(mpc_plan::B_WOEV, p->wo_cap, sizeof(WoEv));
-  set(mpc_plan::B_WOKEY, p->wo_cap ? p->wo_p2 : 0, 8);
-  set(mpc_plan::B_WOIDX, p->wo_cap ? p->wo_p2 : 0, 4);
-  set(mpc_plan::B_WOERUN, 2 * p->wo_cap, 4);  // run of every sorted string, then K_woprep's scratch
-  set(mpc_plan::B_WOPOS, p->wo_cap, sizeof(WoPos));
-  set(mpc_plan::B_WORUN, p->wo_cap ? 2 * p->wo_cap + 1 : 0, sizeof(WoRun));
-  const int64_t wo_x = p->n_shards > 1 ? p->wo_cap : 0;  // the exchange buffers (counts in int32 words but WOCOV)
-  set(mpc_plan::B_WOREC, wo_x * 6, 4);
-  set(mpc_plan::B_WOALL, wo_x ? (wo_x + 1) * 6 : 0, 4);
-  set(mpc_plan::B_WOCOV, wo_x ? 2 * wo_x + 1 : 0, 4);
-  size_t o = 0;
-  for (int b = 0; b < mpc_plan::B_COUNT; ++b) {
-    o = (o + 255) & ~(size_t)255;
-    p->off[b] = o;
-    o += p->sz[b];
-  }
-  // the device side finds the three exchange buffers of the wrapped odd positions from one pointer
-  if (p->off[mpc_plan::B_WOALL] != p->off[mpc_plan::B_WOREC] + (size_t)wo_a256((int64_t)p->sz[mpc_plan::B_WOREC]) ||
-      p->off[mpc_plan::B_WOCOV] != p->off[mpc_plan::B_WOALL] + (size_t)wo_a256((int64_t)p->sz[mpc_plan::B_WOALL])) {
-    delete p;
-    return fail(MPC_E_STATE, "exchange buffers of the wrapped odd positions are not adjacent");
-  }
-  p->ws_bytes = (o + 255) & ~(size_t)255;
-  p->in.h_cs_off = nullptr;  // host array only read while planning
-  *out = p;
-  return MPC_OK;
-}
-
-int mpc_plan_destroy(mpc_plan* p) { delete p; return MPC_OK; }
-
-int mpc_plan_get_info(const mpc_plan* p, mpc_plan_info* info) {
-  if (!p || !info) return fail(MPC_E_ARG, "null argument");
-  info->tally_mode = p->tally_mode;
-  info->parse_window = p->parse_win;
-  info->parse_waves = p->parse_nw;
-  info->parse_lds_bytes = p->parse_lds;
-  info->deferred_placement = p->defer_off > 0 ? 1 : 0;
-  info->reserved = 0;
-  info->parse_workgroups = p->n_parse_wg;
-  info->max_reads_per_workgroup = p->max_wg_reads;
-  info->reads_per_workgroup_cap = wg_reads_cap(p->tally_mode);
-  info->workspace_bytes = (int64_t)p->ws_bytes;
-  info->overrides = p->overrides;
-  return MPC_OK;
-}
-
-// host copies of the parse work tables (tests / tools): n_wg * 4 int32 records
-// {sample, first read, end read, chunks} and n_wg * (MPC_PARSE_CHUNKS + 1)
-// chunk boundaries; either pointer may be NULL; returns the workgroup count
-int mpc_plan_parse_tables(const mpc_plan* p, int32_t* work, int32_t* chunks) {
-  if (!p) return fail(MPC_E_ARG, "null argument");
-  if (work) std::copy(p->work_parse.begin(), p->work_parse.end(), work);
-  if (chunks) std::copy(p->work_wave.begin(), p->work_wave.end(), chunks);
-  return p->n_parse_wg;
-}
-
-int mpc_plan_workspace_bytes(const mpc_plan* p, size_t* bytes) {
-  if (!p || !bytes) return fail(MPC_E_ARG, "null argument");
-  *bytes = p->ws_bytes;
-  return MPC_OK;
-}
-
-int mpc_plan_set_input(mpc_plan* p, const mpc_input* in) {
-  if (!p || !in) return fail(MPC_E_ARG, "null argument");
-  if (in->n_reads != p->N || in->n_samples != p->S || in->cs_bytes > p->in.cs_bytes ||
-      (in->neg_reads > 0) != (p->in.neg_reads > 0))  // (the K_parse the plan bound; the list capacity stays)
-    return fail(MPC_E_ARG, "input shape differs from the plan");
-  p->in = *in;
-  p->in.h_cs_off = nullptr;  // the work split stays the one planned
-  return MPC_OK;
-}
 
 int mpc_plan_bind(mpc_plan* p, void* ws, size_t bytes) {
   if (!p || !ws) return fail(MPC_E_ARG, "null argument");
@@ -4376,34 +3789,6 @@ int mpc_plan_bind(mpc_plan* p, void* ws, size_t bytes) {
   return MPC_OK;
 }
 
-int mpc_plan_buffer(const mpc_plan* p, int which, size_t* off, int64_t* count) {
-  if (!p || !off || !count) return fail(MPC_E_ARG, "null argument");
-  int b;
-  switch (which) {
-    case MPC_BUF_STATUS: b = mpc_plan::B_STATUS; break;
-    case MPC_BUF_CALLS: b = mpc_plan::B_CALLS; break;
-    case MPC_BUF_NCALLS: b = mpc_plan::B_NCALLS; break;
-    case MPC_BUF_MAXDEPTH: b = mpc_plan::B_MAXD; break;
-    case MPC_BUF_ROWS: b = mpc_plan::B_ROWS; break;
-    case MPC_BUF_ROWMETA: b = mpc_plan::B_META; break;
-    case MPC_BUF_RIGHT_CNT: b = mpc_plan::B_RCNT; break;
-    case MPC_BUF_RIGHT_CNT_ALL: b = mpc_plan::B_RCNTALL; break;
-    case MPC_BUF_HASLEFT: b = mpc_plan::B_HASLEFT; break;
-    case MPC_BUF_MAXR: b = mpc_plan::B_MAXR; break;
-    case MPC_BUF_RUN_M: b = mpc_plan::B_M; break;
-    case MPC_BUF_RUN_R: b = mpc_plan::B_RUNR; break;
-    case MPC_BUF_DIFF: b = mpc_plan::B_DIFF; break;
-    case MPC_BUF_SUB: b = mpc_plan::B_SUB; break;
-    case MPC_BUF_WRAP_REC: b = mpc_plan::B_WOREC; break;
-    case MPC_BUF_WRAP_ALL: b = mpc_plan::B_WOALL; break;
-    case MPC_BUF_WRAP_COVER: b = mpc_plan::B_WOCOV; break;
-    default: return fail(MPC_E_ARG, "unknown buffer");
-  }
-  *off = p->off[b];
-  *count = p->cnt[b];
-  return MPC_OK;
-}
-
 // the mixed RIGHT events sorted by (gap, read): the multi-workgroup chain when
 // the plan has many reads (it falls back to K_rsort by itself), else K_rsort
 static void launch_rsort(const mpc_plan* p, const Dev& d, hipStream_t st) {
@@ -4423,7 +3808,7 @@ static void launch_rsort(const mpc_plan* p, const Dev& d, hipStream_t st) {
 int mpc_parse(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   {
     ClearArgs c{};
     bool over = false;
@@ -4471,7 +3856,7 @@ int mpc_parse(mpc_plan* p, void* stream) {
 int mpc_index(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   const int32_t nrb = (int32_t)((p->N + kRS - 1) / kRS);
   // the insertion work units need only the parse: cut in the RIGHT-split launch
   // (one stream: a second one's event fork/join cost more than the overlap, measured)
@@ -4486,7 +3871,7 @@ int mpc_index(mpc_plan* p, void* stream) {
 int mpc_runs(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   if (p->n_shards > 1) {
     hipLaunchKernelGGL(K_runs, dim3(nblk(p->G + 1, kRunsGB)), dim3(kRunsGB), 0, st, d, next_epoch());
     if (p->N > 0) hipLaunchKernelGGL(K_runR, dim3(std::min<unsigned>(nblk(p->N), 1024)), dim3(256), 0, st, d);
@@ -4498,7 +3883,7 @@ int mpc_runs(mpc_plan* p, void* stream) {
 int mpc_tally(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   launch_left(p, d, st);  // (units: mpc_index)
   p->runt_dirty = true;  // until K_ins has mapped (and cleared) the run tallies
   HIPCHK(hipGetLastError());
@@ -4515,7 +3900,7 @@ static void launch_wrap(const mpc_plan* p, const Dev& d, hipStream_t st) {
 int mpc_wrap(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   if (p->n_shards > 1 && p->wo_cap > 0) launch_wrap(p, d, st);  // (one shard: mpc_layout launches them)
   HIPCHK(hipGetLastError());
   return MPC_OK;
@@ -4524,7 +3909,7 @@ int mpc_wrap(mpc_plan* p, void* stream) {
 int mpc_layout(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   if (p->wo_cap > 0) {  // negative starts: the wrapped odd positions first
     if (p->n_shards == 1) launch_wrap(p, d, st);
     else hipLaunchKernelGGL(K_wofold, dim3(std::min<unsigned>(nblk(p->wo_cap, 256), 64)), dim3(256), 0, st, d);
@@ -4539,7 +3924,7 @@ int mpc_layout(mpc_plan* p, void* stream) {
 int mpc_rows(mpc_plan* p, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   hipLaunchKernelGGL(K_ins, dim3(ins_grid(p)), dim3(kUB), 0, st, ins_args(p, d));
   HIPCHK(hipGetLastError());
   p->runt_dirty = false;  // K_ins (enqueued) zeroes every run tally it maps (all runs of all gaps)
@@ -4552,7 +3937,7 @@ int mpc_rows(mpc_plan* p, void* stream) {
 int mpc_consensus(mpc_plan* p, double mdf, double gtf, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   d.mdf = mdf;
   d.gtf = gtf;
   const int64_t R = p->row_cap;
@@ -4566,7 +3951,7 @@ int mpc_consensus(mpc_plan* p, double mdf, double gtf, void* stream) {
 int mpc_profile_kernel(mpc_plan* p, int which, void* stream) {
   NEED_BOUND(p);
   hipStream_t st = (hipStream_t)stream;
-  Dev d = p->dev();
+  Dev d = plan_dev(p);
   if (p->N == 0) return MPC_OK;
   switch (which) {
     case MPC_K_PARSE:  // re-adds the odd tallies: status/tallies are stale until the next mpc_run

@@ -20,7 +20,7 @@
 #include "mpc_device.h"
 #include "mpc_verify.h"
 
-// mpc_kernels.hip: sets the message mpc_last_error() returns
+// mpc_plan.cpp: sets the message mpc_last_error() returns
 __attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
 
 namespace {

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One step per bench config; prints the plan's status words (rows needed,
-mixed RIGHT events M, work units) and geometry.  python3 scripts/plan_stats.py c2 c3 ..."""
+mixed RIGHT events M, work units) and geometry (the planner: csrc/mpc_plan.cpp).
+python3 scripts/plan_stats.py c2 c3 ..."""
 import importlib, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)

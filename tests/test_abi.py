@@ -56,7 +56,7 @@ def test_planner_geometry(pkg):
     """Host-only planning (no device work): every BASELINE config runs K_parse
     with its per-position state in LDS (tally modes 1-3), within the LDS and
     wave budgets, and the reads-per-workgroup cap that keeps the 16-bit LDS
-    tallies exact (mpc_kernels.hip wg_reads_cap) holds."""
+    tallies exact (mpc_geometry.h wg_reads_cap) holds."""
     g = pkg.engine.geometry
     c2 = g([2686, 2686], [100_000, 100_000], 63 << 20)
     assert c2["tally_mode"] == 1 and c2["max_reads_per_workgroup"] <= c2["reads_per_workgroup_cap"] == 32767
@@ -76,7 +76,7 @@ def test_planner_geometry(pkg):
 
 def test_planner_deferred_placement(pkg):
     """K_parse queues insertion events per wave in LDS (mpc_kernels.hip
-    K_parse DP, kDefQ) only with 2 KiB windows in tally mode 1 or 3 with one
+    K_parse DP; mpc_geometry.h kDefQ; planned in mpc_plan.cpp) only with 2 KiB windows in tally mode 1 or 3 with one
     substitution window, and only when the queues fit the LDS budget without
     changing the geometry: C2-C4 take it, C1 and C5 (LDS full) do not; reads
     with negative starts keep inline placement (the plan binds that K_parse)."""
