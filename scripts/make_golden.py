@@ -351,11 +351,30 @@ def long_reference_cases(script):
               "reference of 2^22 - 1 bases, one past the engine's coordinate limit")
 
 
+def call_rule_cases(script):
+    """Explicit tallies (tests/call_util.py tally_sample, with N in the reference
+    wherever no read matches it): every tie class of the call rule (:363-423) in
+    every assignment of its counts to the bases, and tuples on both sides of
+    the two float64 threshold tests (:421, :428), one case per max depth."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import call_util as cu
+    inf = float("inf")
+    runs = {"small_gtf": cu.SETTINGS,
+            "d100": [(-1, 1), (0.29, 1.12), (0.28, 1), (0.3, 1), (1.0, 1.0)],
+            "d10": [(-1, 1), (0.5, 1.10), (0.5, 2.5), (0.1, inf), (1.0, 1.0)]}
+    names = {"small_gtf": "t_call_rule", "d100": "t_call_rule_d100", "d10": "t_call_rule_d10"}
+    for key, name in names.items():
+        ref, reads, paf = cu.sample_files(cu.tally_sample_named(key, True))
+        emit_case(script, name, ref, reads, paf, runs[key],
+                  "tally_sample(%s, ref_n=True): max depth %d" % (key, max(sum(t) for t in cu.TALLY_SAMPLES[key])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref-script", default="/root/reference/src/mapped_paf_read_parser.py")
-    ap.add_argument("--only", default="", help="'unicode' / 'negative' / 'neg_pyint' / 'long': regenerate only the non-ASCII / "
-                                            "negative-tstart / negative-tstart int() / past-the-length-limit cases")
+    ap.add_argument("--only", default="", help="'unicode' / 'negative' / 'neg_pyint' / 'long' / 'call_rule': regenerate only the "
+                                            "non-ASCII / negative-tstart / negative-tstart int() / past-the-length-limit / "
+                                            "explicit-tally cases")
     a = ap.parse_args()
     os.makedirs(GOLDEN, exist_ok=True)
     if a.only == "unicode":
@@ -370,11 +389,15 @@ def main():
     if a.only == "long":
         long_reference_cases(a.ref_script)
         return
+    if a.only == "call_rule":
+        call_rule_cases(a.ref_script)
+        return
     hand_cases(a.ref_script)
     unicode_cases(a.ref_script)
     negative_cases(a.ref_script)
     negative_pyint_cases(a.ref_script)
     long_reference_cases(a.ref_script)
+    call_rule_cases(a.ref_script)
     random_cases(a.ref_script)
 
 
