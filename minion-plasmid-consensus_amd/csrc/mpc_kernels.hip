@@ -3002,7 +3002,8 @@ __global__ __launch_bounds__(kUB) void K_ins(InsArgs a) {
 // whose row offset one ds_bpermute fetches.  Rows of the hot gaps (voted per
 // chunk of reads: for full-length reads gap 0 upstream, gap n downstream) are
 // tallied in LDS windows, everything else with global atomics.  Block
-// barriers: one per chunk (after its records load), and the flush (at the
+// barriers: two per chunk (after its records load, which hands the vote the
+// gaps and rows of three reads, and after the vote), and the flush (at the
 // end, or when a block's chunk range crosses into another sample's gaps).
 // ---------------------------------------------------------------------------
 #ifndef MPC_FLANK_WAVES
@@ -3013,7 +3014,8 @@ constexpr int kFWSmall = 2;     // ... when kFW-wave blocks would not give every
 constexpr int kWinRows = 256;   // LDS window rows per flank side
 constexpr int kFSeg = 256;      // flank bytes per wave step (4 per lane)
 constexpr int kFStageLd = 2;    // 16-byte loads per lane per staged side (2 KiB per wave)
-constexpr int kFStage = kFStageLd * 1024 - 16;  // flank bytes per side staged per wave (C3: 64 reads x 0-40 B, mean 1280)
+constexpr int kFStageBytes = kFStageLd * 64 * 16;  // the stage itself
+constexpr int kFStage = kFStageBytes - 16;  // flank bytes per side staged per wave (C3: 64 reads x 0-40 B, mean 1280)
 // K_flank blocks at most (two per CU): beyond, a block takes a contiguous range of
 // chunks (C3: 1954 one-chunk blocks 135 us, 512 blocks of ~4 chunks 110 us)
 #ifndef MPC_FLANK_BLOCKS_MAX
@@ -3039,25 +3041,19 @@ __device__ __forceinline__ int code_exact(uint32_t c) {
   return c == expect ? code : -1;
 }
 
-// gap of read r's flank on one side (-1: empty flank or no row), for the window vote
-__device__ __forceinline__ int32_t flank_gap(const FlankArgs& a, int64_t r, int side) {
-  const int64_t* off = side ? a.down_off : a.up_off;
-  if (off[r + 1] <= off[r]) return -1;
-  const int s = a.sample[r];
-  const int x = side ? a.i_end[r] : a.tstart[r];
-  return (x >= 0 && x <= a.n_of[s]) ? a.gbase[s] + x : -1;
-}
-
 template <int NW, bool MULTI>  // waves per block; blocks take several chunks (grid capped)
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI || NW < kFW ? 4 : 6))) void K_flank(FlankArgs a) {
   // row r, code c at word 5 r + c: consecutive rows (the bytes of one flank,
   // on consecutive lanes) fall on distinct banks
   __shared__ uint32_t win[2][kWinRows * 5];
   __shared__ __attribute__((aligned(16))) uint32_t own[NW][kFSeg];  // per wave: 1 + lane of the flank starting at each byte
-  __shared__ __attribute__((aligned(16))) uint8_t stg[NW][2][kFStageLd * 64 * 16];  // per wave and side: staged flank bytes
+  __shared__ __attribute__((aligned(16))) uint8_t stg[NW][2][kFStageBytes];  // per wave and side: staged flank bytes
   // the windows' first rows: placed, and voted for the chunk (by chunk parity: a
   // wave still comparing chunk k's vote never sees chunk k + 1's)
   __shared__ int64_t s_w0[2], s_wn[2][2];
+  // per side: the three voters' gap and its first row (written before the chunk's
+  // first barrier, read before its second: no parity needed)
+  __shared__ int2 s_vote[2][3];
   if (a.status[MPC_ST_FLAGS] & (DE_CAP | DE_INTERNAL)) return;
   const int tid = threadIdx.x, l = lane();
   const int w = uniform_i32(tid >> 6);
@@ -3084,14 +3080,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
   uint32_t* ow_w = own[w];
 #pragma unroll 1
   for (int64_t ck = ck0; ck < ck1; ++ck) {
-    if (tid < 2) {  // LDS window: rows of the gap most of the chunk's reads use (vote of 3)
-      const int64_t c0 = ck * RB;
-      const int64_t nr = a.N - c0 < RB ? a.N - c0 : RB;
-      const int32_t x = flank_gap(a, c0, tid), y = flank_gap(a, c0 + nr / 2, tid), z = flank_gap(a, c0 + nr - 1, tid);
-      const int32_t gw = (x == y || x == z) ? x : y;
-      s_wn[ck & 1][tid] = gw >= 0 ? (int64_t)a.row_base[gw] : (int64_t)INT32_MIN;
-      if (ck == ck0) s_w0[tid] = s_wn[ck & 1][tid];  // the first placement (windows zeroed above)
-    }
     const int64_t rb = ck * RB + (int64_t)w * 64;  // the wave's first read
     const int64_t r = rb + l;
     const bool live = r < a.N;
@@ -3102,6 +3090,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
     // the CUs K_flank does not hold
     int64_t off0 = 0, off1 = 0;
     int32_t L0 = 0, L1 = 0, rw0 = -1, rw1 = -1;
+    int2 v0 = make_int2(-1, 0), v1 = make_int2(-1, 0);  // for the vote: each flank's gap (-1: empty flank or no row), the gap's first row
     if (live) {
       const int s = a.sample[r], ts = a.tstart[r], ie = a.i_end[r];
       off0 = a.up_off[r];
@@ -3114,7 +3103,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
         int64_t hi = 0;
         if (a.right_start[g + 1] > a.right_start[g])
           hi = a.hiR[run_left(a.right_start, a.rsl, a.roff, a.vals_out, g, a.read_offset + r)];
-        const int64_t rs = (int64_t)a.row_base[g] + a.lo_f[g] + hi - ul;
+        v0 = make_int2((int32_t)g, a.row_base[g]);
+        const int64_t rs = (int64_t)v0.y + a.lo_f[g] + hi - ul;
         if (rs >= 0 && rs + ul > tot) lerr |= DE_INTERNAL;
         else rw0 = (int32_t)rs;
       }
@@ -3125,14 +3115,33 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
           const int64_t t = a.rpos[r];
           lo_at = a.loR[(int64_t)a.right_start[g] + g + a.roff[g] + (t - a.rsl[g])];
         }
-        const int64_t rs = (int64_t)a.row_base[g] + a.lo_f[g] - lo_at;
+        v1 = make_int2((int32_t)g, a.row_base[g]);
+        const int64_t rs = (int64_t)v1.y + a.lo_f[g] - lo_at;
         if (rs >= 0 && rs + dl > tot) lerr |= DE_INTERNAL;
         else rw1 = (int32_t)rs;
       }
       L0 = ul < INT32_MAX ? (int32_t)ul : INT32_MAX;
       L1 = dl < INT32_MAX ? (int32_t)dl : INT32_MAX;
     }
-    __syncthreads();  // the vote is in; every wave is done with the previous chunk
+    {  // LDS window: rows of the gap most of the chunk's reads use.  A vote of 3
+       // (the chunk's first, middle and last read): their lanes hold the gap and
+       // its first row already, so the vote costs no global load of its own (on
+       // two threads ahead of the records it was five dependent ones, off ->
+       // sample -> tstart -> n_of / gbase -> row_base, that the block waited for)
+      const int64_t c0 = ck * RB;
+      const int64_t nr = a.N - c0 < RB ? a.N - c0 : RB;
+      if (r == c0) { s_vote[0][0] = v0; s_vote[1][0] = v1; }
+      if (r == c0 + nr / 2) { s_vote[0][1] = v0; s_vote[1][1] = v1; }
+      if (r == c0 + nr - 1) { s_vote[0][2] = v0; s_vote[1][2] = v1; }
+    }
+    __syncthreads();  // the votes are in; every wave is done with the previous chunk
+    if (tid < 2) {
+      const int2 x = s_vote[tid][0], y = s_vote[tid][1], z = s_vote[tid][2];
+      const int2 gw = (x.x == y.x || x.x == z.x) ? x : y;
+      s_wn[ck & 1][tid] = gw.x >= 0 ? (int64_t)gw.y : (int64_t)INT32_MIN;
+      if (ck == ck0) s_w0[tid] = s_wn[ck & 1][tid];  // the first placement (windows zeroed above)
+    }
+    __syncthreads();
     const int64_t* wn_ = s_wn[ck & 1];
     if (MULTI && (wn_[0] != s_w0[0] || wn_[1] != s_w0[1])) {  // (block-uniform) windows move: flush, clear, place
       flush();
@@ -3225,17 +3234,45 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
           // stage ahead of the bytes before it
           if (ne && xo >= S && xo < S + kFSeg && xo < c1) ow_w[xo - S] = (uint32_t)(l + 1);
           wave_sync_lds();
+          // The four 64-byte groups of the segment go through each step
+          // TOGETHER: their marks and staged bytes in one batch of LDS reads,
+          // four independent scans (only the scalar carry links the groups),
+          // one batch of ds_bpermute -- two LDS round trips per segment before
+          // the tallies; group after group it was three per group, each
+          // waiting for the previous group's LDS adds as well (LDS completes
+          // in order).  The byte reads are unconditional, so their index stays
+          // inside the stage: only group 3 of a full stage's last segment can
+          // pass it (dead lanes, x >= c1)
+          static_assert(15 + (kFStage - 1) / kFSeg * kFSeg + 191 < kFStageBytes, "groups 0-2 read inside the stage");
+          const int bx = sh + (S - c0) + l;
+          int o[4];
+          uint32_t ch[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) o[k] = (int)ow_w[64 * k + l];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) ch[k] = st[k < 3 ? bx + 64 * k : min(bx + 192, kFStageBytes - 1)];
+          // (all eight are in registers here: none sinks to its use below)
+          asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(ch[0]), "+v"(ch[1]), "+v"(ch[2]), "+v"(ch[3]));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) o[k] = wave_scan_max_i32(o[k]);
+          int32_t q[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int top = wave_last_i32(o[k]);
+            o[k] = max(o[k], carry);  // owner (1 + lane) of byte S + 64 k + l; 0: past the wave's range
+            carry = max(top, carry);  // (= the owner on lane 63: a scalar max, no lane read of the sum)
+            // the row offset of the byte's flank
+            q[k] = __builtin_amdgcn_ds_bpermute(4 * max(o[k] - 1, 0), rowoff);
+          }
+          asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]));
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const int x = S + 64 * k + l;
-            const int inc = max(wave_scan_max_i32((int)ow_w[64 * k + l]), carry);
-            carry = wave_last_i32(inc);
-            // the row offset of the byte's flank (owner 0: bytes past the wave's range)
-            const int32_t q = __builtin_amdgcn_ds_bpermute(4 * max(inc - 1, 0), rowoff);
+            const int inc = o[k];
             if (x >= c1 || inc == 0) continue;
-            const int32_t row = x + q;
+            const int32_t row = x + q[k];
             if (row < 0) continue;  // flank without a row
-            const int code = code_exact(st[sh + (x - c0)]);
+            const int code = code_exact(ch[k]);
             if (code < 0) {
               lerr |= DE_KEY;
               const int64_t rr = rb + inc - 1;
