@@ -9,13 +9,16 @@ Modules
   dist     multi-GPU read sharding over RCCL (torch.distributed)
   verify   exact alignment of consensus files with the expected plasmid (K_vscan)
   coverage per-position depth / deletion / mismatch / insertion profile from the PAF (K_covparse)
+  linkage  per-read alleles at variable sites and their pairwise co-occurrence (K_lnkparse, K_lnkpair)
   mapped_paf_read_parser  the drop-in CLI
   verify_consensus        the "Check the results" CLI
   coverage_qc             the coverage criterion CLI
+  linkage_qc              the sub-population (linked minor alleles) CLI
 """
 from . import _build, ingest, writers, synth  # noqa: F401
 from . import engine  # noqa: F401
 from . import verify  # noqa: F401
 from . import coverage  # noqa: F401
+from . import linkage  # noqa: F401
 
-__all__ = ["ingest", "engine", "writers", "synth", "verify", "coverage"]
+__all__ = ["ingest", "engine", "writers", "synth", "verify", "coverage", "linkage"]

@@ -1,11 +1,12 @@
 """In-tree builds of the native libraries (no JIT cache: the .so files travel with
 the repo snapshot to the GPU box).
 
-  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan, mpc_coverage.h: K_covparse), hipcc --offload-arch=gfx950;
+  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan, mpc_coverage.h: K_covparse, mpc_linkage.h: K_lnkparse), hipcc --offload-arch=gfx950;
                    its host planner (csrc/mpc_plan.cpp) with g++
   libmpc_synth.so  host-only synthetic data generator (g++)
   libmpc_ingest.so native host I/O: ingest (Steps 1-3) and writers (Step 7) (include/mpc_ingest.h, g++ -pthread)
-                   and the host halves of verify_consensus (include/mpc_verify.h) and coverage_qc (mpc_coverage.h)
+                   and the host halves of verify_consensus (include/mpc_verify.h), coverage_qc (mpc_coverage.h)
+                   and linkage_qc (mpc_linkage.h)
 """
 import os
 import subprocess
@@ -19,9 +20,9 @@ LIBMPC = os.path.join(PKG, "libmpc.so")
 LIBSYNTH = os.path.join(PKG, "libmpc_synth.so")
 LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 
-HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip"]
+HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip", "mpc_link.hip"]
 HOST_SOURCES = ["mpc_plan.cpp"]  # libmpc.so's host planner (g++, no HIP)
-HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h"]
+HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h"]
 
 
 def _stale(target, sources):
@@ -43,8 +44,8 @@ def ensure_synth():
 
 
 def build_ingest(force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp")]
-    hdrs = [os.path.join(INCLUDE, h) for h in ("mpc_ingest.h", "mpc_verify.h", "mpc_coverage.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp")]
+    hdrs = [os.path.join(INCLUDE, h) for h in ("mpc_ingest.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h")]
     if force or _stale(LIBINGEST, srcs + hdrs + [os.path.join(CSRC, "host_threads.h")]):
         subprocess.run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I", INCLUDE, "-o", LIBINGEST] + srcs,
                        check=True)
@@ -56,7 +57,7 @@ def build_hip(force=False, extra=(), out=None):
     out = out or LIBMPC
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     host = [os.path.join(CSRC, s) for s in HOST_SOURCES]
-    deps = srcs + host + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h", "mpc_coverage.h")]
+    deps = srcs + host + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h")]
     if force or extra or _stale(out, deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         flags = ["-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC] + list(extra)

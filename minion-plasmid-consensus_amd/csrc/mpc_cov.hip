@@ -4,14 +4,10 @@
 //
 // K_covparse: one wave64 per record, workgroups of 16 waves over a contiguous
 // cut of the records.  The cs is taken in tiles of 64 x kCovK bytes (kCovK
-// non-temporal byte loads per lane in flight), one 64-byte chunk at a time:
-// classify the byte per lane, ballot the operators, let every operator lane own
-// its token (lane 0 owns the token still open from the chunk before), read the
-// token's reference advance, prefix-scan the advances over the wave to give
-// every token its p, emit.  Carried from chunk to chunk (wave-uniform): p, the
-// open operator, the number read so far and its digit count / the letters of an
-// open run.  A '-' run that crosses a chunk is emitted in pieces; ':' and '*'
-// take effect where they close.
+// non-temporal byte loads per lane in flight), one 64-byte chunk at a time,
+// by the tokenizer K_lnkparse shares (cs_chunk, mpc_cswalk.h): it gives every
+// token its p; what a token does to the pileup is CovFx below.  A '-' run that
+// crosses a chunk is emitted in pieces; ':' and '*' take effect where they close.
 //
 // What is written: aligned u deleted of a record is exactly [tstart, final p),
 // so the depth column takes ONE +1 / -1 pair per record (its span) and the
@@ -31,6 +27,7 @@
 
 #include "mpc.h"
 #include "mpc_coverage.h"
+#include "mpc_cswalk.h"
 #include "mpc_device.h"
 
 // mpc_plan.cpp: sets the message mpc_last_error() returns
@@ -42,8 +39,7 @@ using namespace mpc;
 typedef long long i64;
 typedef unsigned long long u64;
 
-constexpr int kCovK = 4;                  // 64-byte chunks per tile
-constexpr int kCovTile = 64 * kCovK;
+constexpr int kCovK = kCsK, kCovTile = kCsTile;  // the tile of the shared walk
 constexpr int kCovWaves = 16;
 constexpr int kCovThreads = 64 * kCovWaves;
 constexpr int kCovHalf = 2048;            // LDS slice: rows [0, kCovHalf) and the last kCovHalf rows
@@ -76,143 +72,38 @@ struct Sink {
   }
 };
 
-// wave-uniform state of a record's walk
-struct Walk {
-  i64 p;           // current position (at most L while !oor)
-  uint32_t num;    // value of an open number
-  int32_t op, cnt; // open operator (0: none) and its operand bytes so far
-  bool bad, oor;
-};
-
 // per-lane partial counts of ONE record (slots 1-6; a record's cs is shorter than 2^31 bytes)
 struct Counts {
   uint32_t match, mism, insev, insb, delev, delb;
 };
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, int j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, j); }
-__device__ __forceinline__ i64 rl64(i64 v, int j) {
-  return (i64)(((u64)rl((uint32_t)((u64)v >> 32), j) << 32) | rl((uint32_t)v, j));
-}
-
-constexpr int kCovFastAdv = 1 << 25;  // 32 tokens of a chunk x this stays inside 32 bits
-
-// one 64-byte chunk: lane ln holds byte c (valid below nvalid); last: the cs ends in this chunk
-__device__ __forceinline__ void cov_chunk(const uint32_t c, const int nvalid, const bool last, const uint32_t L,
-                                          const uint64_t lemask, const Sink& out, Walk& w, Counts& t) {
-  const int ln = lane();
-  const bool valid = ln < nvalid;
-  const uint32_t x = c - 0x2au;  // '*' 0, '+' 1, '-' 3, ':' 16
-  const bool isop = valid && x <= 16u && ((0x1000bu >> x) & 1u);
-  const bool isdig = (c - '0') < 10u;
-  const bool islet = ((c | 32u) - 'a') < 26u;
-  const uint64_t opm = ballot(isop);
-  const uint64_t colons = ballot(isop && c == ':');
-  bool lbad = false, loor = false;
-  i64 p0 = w.p;
-
-  // the token left open by the chunk before ends at an operator in lane 0
-  if ((opm & 1ull) && w.op) {
-    if (w.op == ':') {
-      if (w.cnt < 1) lbad = true;
-      else { if (ln == 0) t.match += w.num; p0 += w.num; }
-    } else if (w.op == '*') {
-      if (w.cnt != 2) lbad = true;
-      else {
-        if (ln == 0) {
-          ++t.mism;
-          if (!w.oor) { if (p0 < (i64)L) out.add((uint32_t)p0, 2, 1u); else loor = true; }
-        }
-        p0 += 1;
-      }
-    } else if (w.cnt < 1) lbad = true;
-    if (p0 > (i64)L) w.oor = true;
+// what a token does to the pileup (the effects policy of cs_chunk, mpc_cswalk.h)
+struct CovFx {
+  static constexpr bool kBase = false;
+  const Sink& out;
+  Counts& t;
+  __device__ __forceinline__ void carried_match(uint32_t num) const { if (lane() == 0) t.match += num; }
+  __device__ __forceinline__ void carried_sub() const { ++t.mism; }
+  __device__ __forceinline__ void carried_sub_at(uint32_t p) const { out.add(p, 2, 1u); }
+  __device__ __forceinline__ void count(bool num_close, uint32_t v, bool hit, bool k_del, bool k_ins, int cnt, bool isop) const {
+    t.match += num_close ? v : 0u;
+    t.mism += hit;
+    t.delb += k_del ? (uint32_t)cnt : 0u;
+    t.delev += k_del && isop;
+    t.insb += k_ins ? (uint32_t)cnt : 0u;
+    t.insev += k_ins && isop;
   }
-
-  // the operator that governs this lane's byte: the highest operator at or below the lane, else the open one
-  const uint64_t below = opm & lemask;
-  const bool gov_colon = below ? (below & colons) > (below & ~colons) : w.op == ':';
-  // (an operand byte before any operator has no governor)
-  lbad |= valid && !isop && ((!below && !w.op) || (gov_colon ? !isdig : !islet));
-
-  // token owners: operator lanes, and lane 0 for the open token when it continues here
-  const bool own = isop || (ln == 0 && valid);
-  const uint32_t kind = isop ? c : (uint32_t)w.op;
-  const int s = isop ? ln + 1 : 0;                  // first operand lane
-  const uint64_t above = s < 64 ? opm >> s : 0ull;  // operators from there on
-  const int nx = above ? s + __ffsll((i64)above) - 1 : nvalid;
-  const int cnt = nx - s;                           // operand bytes in this chunk
-  const bool closed = above != 0 || last;
-  const int tot = (isop ? 0 : w.cnt) + cnt;
-  const bool isnum = own && kind == ':' && tot <= 9;
-  uint32_t v = isop ? 0u : w.num;
-  for (int d = 0; d < 9; ++d) {
-    if (!ballot(isnum && d < cnt)) break;
-    const uint32_t dg = (uint32_t)__shfl((int)c, s + d < 63 ? s + d : 63, 64) - '0';
-    if (isnum && d < cnt) v = (v << 3) + (v << 1) + dg;  // (shift-adds: v_mul_lo_u32 is quarter rate)
-  }
-
-  // what the token does, as selects: nested branches on the kind cost more than the arithmetic
-  const bool k_num = own && kind == ':', k_sub = own && kind == '*', k_del = own && kind == '-', k_ins = own && kind == '+';
-  lbad |= (k_num && (tot > 9 || (closed && tot < 1))) || (k_sub && (tot > 2 || (closed && tot != 2))) ||
-          ((k_del || k_ins) && closed && tot < 1);
-  const bool num_close = k_num && closed && tot >= 1 && tot <= 9;
-  const bool hit = k_sub && closed && tot == 2;  // a mismatch closes here
-  const int adv = num_close ? (int)v : hit ? 1 : k_del ? cnt : 0;
-  t.match += num_close ? v : 0u;
-  t.mism += hit;
-  t.delb += k_del ? (uint32_t)cnt : 0u;
-  t.delev += k_del && isop;
-  t.insb += k_ins ? (uint32_t)cnt : 0u;
-  t.insev += k_ins && isop;
-  if (!isnum) v = 0;
-
-  // every token's p: a wave prefix scan of the advances (32-bit while no run is longer than 2^25)
-  uint32_t pos;
-  if (!ballot(adv > kCovFastAdv)) {
-    const int incl = wave_scan_i32(adv);
-    pos = (uint32_t)p0 + (uint32_t)(incl - adv);
-    w.p = p0 + wave_last_i32(incl);
-  } else {
-    const i64 incl = wave_incl_scan<i64>((i64)adv);
-    const i64 at = p0 + incl - adv;
-    pos = at > (i64)L ? 0x80000000u : (uint32_t)at;  // (past L: refused below whatever it is)
-    w.p = p0 + rl64(incl, 63);
-  }
-
-  // at most two words per token: a point, or the two ends of a deletion piece
-  const bool del_piece = k_del && cnt > 0, ins_at = k_ins && isop;
-  const uint32_t reach = pos + (del_piece ? (uint32_t)cnt : 0u);
-  const bool wants = hit || del_piece || ins_at;
-  const bool fits = hit ? pos < L : reach <= L;
-  loor = loor || (wants && !w.oor && !fits);
-  if (wants && fits && !w.oor) {
+  __device__ __forceinline__ bool look(i64, i64) const { return true; }
+  __device__ __forceinline__ void emit(bool hit, bool del_piece, uint32_t pos, uint32_t reach, uint32_t) const {
     out.add(pos, hit ? 2 : del_piece ? 1 : 3, 1u);
     if (del_piece) out.add(reach, 1, ~0u);
   }
-
-  // what stays open
-  if (nvalid > 0) {
-    const int j = uniform_i32(opm ? 63 - __clzll((i64)opm) : 0);
-    if (opm) w.op = (int32_t)rl(c, j);
-    w.cnt = (int32_t)rl((uint32_t)tot, j);
-    w.num = rl(v, j);
-  }
-  w.bad |= ballot(lbad) != 0;
-  w.oor |= ballot(loor) != 0 || w.p > (i64)L;
-}
+};
 
 __device__ __forceinline__ void cov_report(uint64_t* stats, i64 r, int code) {
   // the smallest record wins, malformed before out of range: the largest inverted key
   const u64 key = ~((u64)r * 2 + (code == MPC_COV_RANGE ? 1 : 0));
   __hip_atomic_fetch_max((u64*)&stats[kErrSlot], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void cov_load_tile(uint32_t (&bt)[kCovK], const uint8_t* q, int len, int t0) {
-#pragma unroll
-  for (int k = 0; k < kCovK; ++k) {
-    const int i = t0 + k * 64 + lane();
-    bt[k] = i < len ? (uint32_t)__builtin_nontemporal_load(q + i) : 0u;
-  }
 }
 
 // grid: workgroups over contiguous cuts of per_wg records; wave w of a workgroup takes every 16th.
@@ -268,7 +159,7 @@ __global__ __launch_bounds__(kCovThreads) void K_covparse(
     uint32_t nb[kCovK];
     const uint8_t* q = cs + rl64(m_a, 0);
     int len = (int32_t)rl((uint32_t)m_len, 0);
-    cov_load_tile(nb, q, len, 0);
+    cs_load_tile(nb, q, len, 0);
     for (int j = 0; j < count; ++j) {
       const i64 r = rb + (i64)kCovWaves * j;
       const int32_t s = (int32_t)rl((uint32_t)m_s, j);
@@ -281,7 +172,7 @@ __global__ __launch_bounds__(kCovThreads) void K_covparse(
       if (j + 1 < count) {
         q = cs + rl64(m_a, j + 1);
         len = (int32_t)rl((uint32_t)m_len, j + 1);
-        cov_load_tile(nb, q, len, 0);
+        cs_load_tile(nb, q, len, 0);
       }
       if (s < 0) {
         if (ln == 0) cov_report(stats, r, MPC_COV_RANGE);
@@ -291,12 +182,13 @@ __global__ __launch_bounds__(kCovThreads) void K_covparse(
       Walk w = {ts, 0u, 0, 0, clen < 0, ts < 0 || ts > (i64)L};
       const Sink out = {rows + base * 4, s == sl.sample ? tab : nullptr, nrows};
       Counts t = {0, 0, 0, 0, 0, 0};
+      CovFx fx = {out, t};
       for (int t0 = 0; t0 < clen && !w.bad; t0 += kCovTile) {
-        if (t0 > 0) cov_load_tile(bt, cq, clen, t0);
+        if (t0 > 0) cs_load_tile(bt, cq, clen, t0);
 #pragma unroll
         for (int k = 0; k < kCovK; ++k) {
           const int cb = t0 + k * 64;
-          if (cb < clen && !w.bad) cov_chunk(bt[k], clen - cb < 64 ? clen - cb : 64, cb + 64 >= clen, L, lemask, out, w, t);
+          if (cb < clen && !w.bad) cs_chunk(bt[k], clen - cb < 64 ? clen - cb : 64, cb + 64 >= clen, L, lemask, fx, w);
         }
       }
       if (w.bad || w.oor) {

@@ -1,0 +1,156 @@
+"""linkage_qc on the host: mpc_linkage_host / mpc_linkage_pairs_host
+(device="cpu") against the independent checker of tests/link_util.py, over the
+cases test_linkage_gpu.py runs on the device, the tables the host refuses, the
+site selection, the statistics, the CLI and the host code under ASan + UBSan."""
+import os
+
+import numpy as np
+import pytest
+
+import cov_util as cu
+import link_util as lu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(REPO, "minion-plasmid-consensus_amd", "linkage_qc.py")
+DEV = "cpu"
+
+
+def test_boundaries(pkg):
+    lu.case_boundaries(pkg, DEV)
+
+
+def test_ends_of_record_and_target(pkg):
+    lu.case_ends(pkg, DEV)
+
+
+@pytest.mark.parametrize("n,k", lu.PAIR_SHAPES)
+def test_pairs_shapes(pkg, n, k):
+    lu.case_pairs_shape(pkg, DEV, n, k)
+
+
+def test_pairs_one_code_past_16_bits(pkg):
+    lu.case_pairs_one_code(pkg, DEV)
+
+
+def test_pairs_limits(pkg):
+    lu.case_pairs_limits(pkg, DEV)
+
+
+def test_samples(pkg):
+    lu.case_samples(pkg, DEV)
+
+
+def test_more_records_than_waves_and_determinism(pkg):
+    lu.case_one_token(pkg, DEV)
+
+
+@pytest.mark.parametrize("name,rec,code", cu.BAD, ids=[b[0] for b in cu.BAD])
+def test_status_parity_with_coverage(pkg, name, rec, code):
+    lu.case_status_parity(pkg, DEV, rec, code)
+
+
+def test_status_smaller_index_wins_far_apart(pkg):
+    lu.case_status_far_apart(pkg, DEV)
+
+
+def test_host_refuses_bad_tables_untouched(pkg):
+    L = pkg.linkage.host_lib()
+    cs = np.frombuffer(b":3" + b"\0" * 6, np.uint8)
+    off, ts, smp = np.array([0, 2], np.int64), np.zeros(1, np.int64), np.zeros(1, np.int32)
+    pos = np.array([0, 11, 18], np.int64)
+    alleles, pair, status = np.full(3, 9, np.uint8), np.full(9 * 64, 9, np.uint32), np.full(2, 9, np.int32)
+
+    def call(site_off, site_key, k):
+        so, sk = np.array(site_off, np.int64), np.array(site_key, np.int64)
+        return L.mpc_linkage_host(cs.ctypes.data, off.ctypes.data, ts.ctypes.data, smp.ctypes.data, 1, pos.ctypes.data, 2,
+                                  so.ctypes.data, sk.ctypes.data, k, alleles.ctypes.data, pair.ctypes.data, status.ctypes.data, 1)
+    for site_off, site_key, k, word in lu.BAD_TABLES:
+        assert call(site_off, site_key, k) == -1 and word in L.mpc_linkage_last_error(), (site_off, site_key)
+        assert (alleles == 9).all() and (pair == 9).all() and (status == 9).all()
+    assert call([0] + [64] * 2, list(range(129)), 129) == -1 and b"n_sites" in L.mpc_linkage_last_error()
+    assert (pair == 9).all()
+    assert call(*lu.GOOD_TABLE) == 0
+    assert alleles.tolist() == [1, 0, 0] and status.tolist() == [0, 0] and pair.reshape(3, 3, 8, 8)[0, 1, 1, 0] == 1
+
+
+def test_select_sites_keeps_the_highest_fractions(pkg):
+    rows = np.zeros((11, 4), np.uint32)  # one 10-base target, depth 100 everywhere
+    rows[:10, 0] = 100
+    rows[2, 2], rows[4, 1], rows[4, 0], rows[6, 3], rows[8, 2], rows[10, 3] = 30, 20, 80, 25, 30, 40
+    off, key, dropped = pkg.linkage.select_sites(rows, [0, 11], [(0, 10)], 0.05, 10)
+    assert key.tolist() == [lu.base(2), lu.base(4), lu.gap(6), lu.base(8), lu.gap(10)] and off.tolist() == [0, 5] and dropped == 0
+    off, key, dropped = pkg.linkage.select_sites(rows, [0, 11], [(0, 10)], 0.05, 10, max_sites=3)
+    assert key.tolist() == [lu.base(2), lu.base(8), lu.gap(10)] and dropped == 2  # 0.4, then the tie at 0.3 by key
+    off, key, dropped = pkg.linkage.select_sites(rows, [0, 11], [(3, 9)], 0.25, 10)
+    assert key.tolist() == [lu.gap(6), lu.base(8)]  # the gap at L belongs to a region that reaches L
+    assert not len(pkg.linkage.select_sites(rows, [0, 11], [(0, 10)], 0.05, 31)[1][:-1])
+
+
+def test_pair_stats_definition(pkg):
+    pair = np.zeros((2, 2, 8, 8), np.uint32)
+    # codes (site 0, site 1): 50 x (1, 1), 30 x (4, 7), 10 x (4, 1), 5 x (1, 7), 7 x (0, 7), 3 x (1, 0)
+    for a, b, n in ((1, 1, 50), (4, 7, 30), (4, 1, 10), (1, 7, 5), (0, 7, 7), (1, 0, 3)):
+        pair[0, 1, a, b] += n
+        pair[1, 0, b, a] += n
+        pair[0, 0, a, a] += n
+        pair[1, 1, b, b] += n
+    st = pkg.linkage.pair_stats(pair, 0, 1, 0.1, 10)
+    assert (st["major_i"], st["major_j"], st["n"], st["x"], st["y"], st["n11"]) == (1, 1, 95, 40, 35, 30)
+    assert st["r2"] == (95 * 30 - 40 * 35) ** 2 / (40 * 55 * 35 * 60) and st["linked"]
+    assert not pkg.linkage.pair_stats(pair, 0, 1, 0.1, 31)["linked"] and not pkg.linkage.pair_stats(pair, 0, 1, 0.9, 10)["linked"]
+    tie = np.zeros((1, 1, 8, 8), np.uint32)
+    tie[0, 0, 3, 3] = tie[0, 0, 2, 2] = 4
+    assert pkg.linkage.major_code(tie, 0) == 2
+    tie[0, 0, 3, 3] = 0  # no minor allele: the denominator is 0
+    st = pkg.linkage.pair_stats(tie, 0, 0)
+    assert (st["n"], st["x"], st["r2"], st["linked"]) == (4, 0, 0.0, False)
+
+
+def test_planted_subpopulation(pkg):
+    lu.case_planted(pkg, DEV)
+
+
+def test_planted_subpopulation_cli(pkg, tmp_path):
+    lu.case_planted_cli(pkg, DEV, tmp_path, CLI)
+
+
+def test_cli_sites_file_and_invalid_input(pkg, tmp_path):
+    import subprocess
+    import sys
+    paf = tmp_path / "mixed.paf"
+    lu.write_paf(str(paf), lu.planted()[0], ["plasmid"], [300])
+    sites = tmp_path / "sites.tsv"
+    sites.write_text("plasmid\t51\tbase\nplasmid\t201\tgap\nplasmid\t301\tgap\n")
+    rep = tmp_path / "rep.tsv"
+    run = lambda *extra: subprocess.run([sys.executable, CLI, "--paf", str(paf), "--report", str(rep), "--device", "cpu"] + list(extra),
+                                        capture_output=True, text=True, timeout=300)
+    p = run("--sites", str(sites))
+    assert p.returncode == 0, p.stderr[-2000:]
+    text = rep.read_text().splitlines()
+    assert "site_list\t51:base,201:gap,301:gap" in text and "linked_pairs\t1" in text and text[-1] == "verdict\tFAIL"
+    rep.unlink()
+    sites.write_text("plasmid\t302\tgap\n")
+    p = run("--sites", str(sites))
+    assert p.returncode == 1 and "outside" in p.stderr and not rep.exists()
+    sites.write_text("other\t5\tbase\n")
+    assert run("--sites", str(sites)).returncode == 1 and not rep.exists()
+    sites.write_text("plasmid\tfive\tbase\n")
+    assert run("--sites", str(sites)).returncode == 1 and not rep.exists()
+    bad = tmp_path / "bad.paf"
+    bad.write_text(paf.read_text().splitlines()[0].replace("cs:Z::", "cs:Z:=") + "\n")
+    p = subprocess.run([sys.executable, CLI, "--paf", str(bad), "--report", str(rep), "--device", "cpu"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 1 and "malformed" in p.stderr and not rep.exists()
+
+
+def test_synth_batch_site_count(pkg):
+    cs, off, ts, rs, lengths, site_off, site_key, dropped = lu.synth_sites(pkg)
+    assert 8 <= len(site_key) <= 128 and dropped == 0 and len(site_off) == 5
+    records = [(int(rs[r]), int(ts[r]), cs.tobytes()[off[r]:off[r + 1]]) for r in range(len(ts))]
+    status, alleles, pair = lu.check(records, lengths, site_off, site_key)
+    got_a, got_p = pkg.linkage.run(cs, off, ts, rs, lengths, site_off, site_key, device=DEV)
+    assert status == (cu.OK, 0) and np.array_equal(got_a, alleles) and np.array_equal(got_p, pair)
+
+
+def test_host_code_sanitized(pkg, tmp_path):
+    lu.case_sanitized_driver(pkg, tmp_path, REPO)
