@@ -110,6 +110,52 @@ def read_paf(path, mode=0, threads=0):
         L.mpc_coverage_ingest_free(ctypes.byref(out))
 
 
+def batch_front(err, cs, cs_off, tstart, rec_sample, lengths, more=()):
+    """The front of coverage.run and linkage.run: (cs, cs_off, tstart, rec_sample,
+    pos_off) as contiguous arrays of the C-ABI's types, checked; what is wrong
+    raises err.  more: [(fault found, message)] of the caller's own tables,
+    reported once the record and target counts stand."""
+    cs = np.ascontiguousarray(cs, np.uint8)
+    cs_off = np.ascontiguousarray(cs_off, np.int64)
+    tstart = np.ascontiguousarray(tstart, np.int64)
+    rec_sample = np.ascontiguousarray(rec_sample, np.int32)
+    n, S = len(tstart), len(lengths)
+    if len(cs_off) != n + 1 or len(rec_sample) != n:
+        raise err("cs_off, tstart and rec_sample disagree on the number of records")
+    if S < 1:
+        raise err("no target")
+    for bad, message in more:
+        if bad:
+            raise err(message)
+    if n and (cs_off[0] < 0 or (np.diff(cs_off) < 0).any() or cs_off[-1] > len(cs)):
+        raise err("cs_off does not cut the cs bytes")
+    if n and (rec_sample.min() < 0 or rec_sample.max() >= S):
+        raise err("a record names a target outside [0, {})".format(S))
+    pos_off = np.zeros(S + 1, np.int64)
+    pos_off[1:] = np.cumsum(np.asarray(lengths, np.int64) + 1)
+    if min(lengths) < 0 or pos_off[-1] >= 2 ** 31:
+        raise err("target lengths must be >= 0 and sum (with one extra row each) to below 2^31")
+    return cs, cs_off, tstart, rec_sample, pos_off
+
+
+def upload(torch, dev, parts):
+    """Device pointers of the numpy arrays `parts`, and the tensor that owns
+    them: one blob, one H2D copy (int64 tables first keeps them 8-byte aligned),
+    8 spare bytes behind the last part."""
+    parts = list(parts) + [np.zeros(8, np.uint8)]
+    offs = np.cumsum([0] + [p.nbytes for p in parts])
+    blob = np.concatenate([p.view(np.uint8).reshape(-1) for p in parts])
+    d_blob = torch.empty(len(blob), dtype=torch.uint8, device=dev)
+    d_blob.copy_(torch.from_numpy(blob))
+    return [d_blob.data_ptr() + int(o) for o in offs[:-2]], d_blob
+
+
+def raise_status(err, status):
+    """The C-ABI's status {code, smallest offending record} as err, if any."""
+    if status[0] != 0:
+        raise err("record {}: {}".format(int(status[1]), CODES.get(int(status[0]), "code %d" % status[0])))
+
+
 def run(cs, cs_off, tstart, rec_sample, lengths, regions=None, min_depth=0, device=0, threads=0, tend=None):
     """dict(rows u32[n_pos][4] = {depth, deleted, mismatch, insertion}, stats
     u64[S][16], pos_off) of the records (cs bytes, cs_off[n + 1], tstart[n],
@@ -118,24 +164,9 @@ def run(cs, cs_off, tstart, rec_sample, lengths, regions=None, min_depth=0, devi
     malformed or out-of-range record.  tend (optional): the PAF's target ends;
     the host path checks every record's walk against it, both paths check the
     aggregate sum(tend - tstart) == match + mismatch + deleted per sample."""
-    cs = np.ascontiguousarray(cs, np.uint8)
-    cs_off = np.ascontiguousarray(cs_off, np.int64)
-    tstart = np.ascontiguousarray(tstart, np.int64)
-    rec_sample = np.ascontiguousarray(rec_sample, np.int32)
+    cs, cs_off, tstart, rec_sample, pos_off = batch_front(CoverageError, cs, cs_off, tstart, rec_sample, lengths)
     n, S = len(tstart), len(lengths)
-    if len(cs_off) != n + 1 or len(rec_sample) != n:
-        raise CoverageError("cs_off, tstart and rec_sample disagree on the number of records")
-    if S < 1:
-        raise CoverageError("no target")
-    if n and (cs_off[0] < 0 or (np.diff(cs_off) < 0).any() or cs_off[-1] > len(cs)):
-        raise CoverageError("cs_off does not cut the cs bytes")
-    if n and (rec_sample.min() < 0 or rec_sample.max() >= S):
-        raise CoverageError("a record names a target outside [0, {})".format(S))
-    pos_off = np.zeros(S + 1, np.int64)
-    pos_off[1:] = np.cumsum(np.asarray(lengths, np.int64) + 1)
-    if min(lengths) < 0 or pos_off[-1] >= 2 ** 31:
-        raise CoverageError("target lengths must be >= 0 and sum (with one extra row each) to below 2^31")
-    region = np.array([(0, L) for L in lengths] if regions is None else regions, np.int64).reshape(S, 2)
+    region =np.array([(0, L) for L in lengths] if regions is None else regions, np.int64).reshape(S, 2)
     for s, (lo, hi) in enumerate(region):
         if not 0 <= lo <= hi <= lengths[s]:
             raise CoverageError("target {}: region {}:{} is outside 0:{}".format(s, lo, hi, lengths[s]))
@@ -158,17 +189,12 @@ def run(cs, cs_off, tstart, rec_sample, lengths, regions=None, min_depth=0, devi
         if not torch.cuda.is_available():
             raise engine.MpcError("no HIP device visible (use device='cpu' for the host walk)")
         dev = torch.device("cuda", int(device))
-        # one blob, one H2D copy: the int64 tables first (8-byte aligned), then rec_sample, then the cs bytes
-        parts = [cs_off, tstart, pos_off, region.reshape(-1), rec_sample, cs, np.zeros(8, np.uint8)]
-        offs = np.cumsum([0] + [p.nbytes for p in parts])
-        blob = np.concatenate([p.view(np.uint8).reshape(-1) for p in parts])
         with torch.cuda.device(dev):
-            d_blob = torch.empty(len(blob), dtype=torch.uint8, device=dev)
-            d_blob.copy_(torch.from_numpy(blob))
+            # the int64 tables first, then rec_sample, then the cs bytes
+            at, d_blob = upload(torch, dev, [cs_off, tstart, pos_off, region.reshape(-1), rec_sample, cs])
             d_rows = torch.empty((n_pos, 4), dtype=torch.int32, device=dev)
             d_stats = torch.empty((S, STATS), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            at = [d_blob.data_ptr() + int(o) for o in offs]
             stream = torch.cuda.current_stream(dev)
             engine._check(L.mpc_coverage_run(at[5], at[0], at[1], at[4], n, at[2], at[3], S, min_depth,
                                              d_rows.data_ptr(), d_stats.data_ptr(), d_status.data_ptr(),
@@ -176,8 +202,7 @@ def run(cs, cs_off, tstart, rec_sample, lengths, regions=None, min_depth=0, devi
             status = d_status.cpu().numpy()
             rows = d_rows.cpu().numpy().view(np.uint32)
             stats = d_stats.cpu().numpy().view(np.uint64)
-    if status[0] != 0:
-        raise CoverageError("record {}: {}".format(int(status[1]), CODES.get(int(status[0]), "code %d" % status[0])))
+    raise_status(CoverageError, status)
     if tend is not None:
         tend = np.asarray(tend, np.int64)
         if rec_out is not None:

@@ -15,13 +15,14 @@
 #include <cstring>
 #include <string>
 #include <string_view>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 #include "host_threads.h"
 #include "mpc_coverage.h"
+#include "mpc_cstables.h"
+#include "mpc_cswalk_host.h"
 
 namespace {
 
@@ -35,81 +36,27 @@ int cfail(const std::string& msg) {
   return kArg;
 }
 
-template <class F>
-void parallel(int T, F f) {
-  if (T <= 1) { f(0); return; }
-  std::vector<std::thread> th;
-  th.reserve((size_t)T);
-  for (int k = 0; k < T; ++k) th.emplace_back(f, k);
-  for (auto& t : th) t.join();
-}
-
-inline bool is_letter(uint8_t c) { return (uint8_t)((c | 32) - 'a') < 26; }
-inline bool is_digit(uint8_t c) { return (uint8_t)(c - '0') < 10; }
+using mpc_host::parallel;
 
 // ---------------------------------------------------------------- the walk
 
-struct RecCounts {
-  uint64_t match = 0, mism = 0, insev = 0, insb = 0, delev = 0, delb = 0;
-};
-
-// One record, straight from the definition.  row: the sample's first row
-// (u32[L + 1][4]).  Returns MPC_COV_*; malformed wins over out of range, so the
-// grammar is followed to the end of the cs even once p has left the target.
-int walk(const uint8_t* q, int64_t len, int64_t ts, int64_t L, uint32_t* row, RecCounts* rc, int64_t* end) {
-  if (len < 0) return MPC_COV_MALFORMED;
-  if (len >= 2 && q[0] == 'Z' && q[1] == ':') { q += 2; len -= 2; }
-  bool oor = ts < 0 || ts > L;
-  int64_t p = ts, k = 0;
-  while (k < len) {
-    const uint8_t op = q[k++];
-    const int64_t a = k;
-    if (op == ':') {
-      int64_t n = 0;
-      while (k < len && is_digit(q[k])) {
-        if (k - a == 9) return MPC_COV_MALFORMED;  // a tenth digit
-        n = n * 10 + (q[k++] - '0');
-      }
-      if (k == a) return MPC_COV_MALFORMED;
-      if (!oor && p + n <= L) {
-        for (int64_t i = 0; i < n; ++i) ++row[(p + i) * 4 + 0];
-      } else oor = true;
-      if (!oor) { p += n; rc->match += (uint64_t)n; }
-    } else if (op == '*') {
-      if (len - k < 2 || !is_letter(q[k]) || !is_letter(q[k + 1])) return MPC_COV_MALFORMED;
-      k += 2;
-      if (k < len && is_letter(q[k])) return MPC_COV_MALFORMED;
-      if (!oor && p < L) {
-        ++row[p * 4 + 0];
-        ++row[p * 4 + 2];
-        ++p;
-        ++rc->mism;
-      } else oor = true;
-    } else if (op == '-' || op == '+') {
-      while (k < len && is_letter(q[k])) ++k;
-      const int64_t n = k - a;
-      if (n == 0) return MPC_COV_MALFORMED;
-      if (op == '-') {
-        if (!oor && p + n <= L) {
-          for (int64_t i = 0; i < n; ++i) ++row[(p + i) * 4 + 1];
-          p += n;
-          ++rc->delev;
-          rc->delb += (uint64_t)n;
-        } else oor = true;
-      } else {
-        if (!oor && p <= L) {
-          ++row[p * 4 + 3];
-          ++rc->insev;
-          rc->insb += (uint64_t)n;
-        } else oor = true;
-      }
-    } else {
-      return MPC_COV_MALFORMED;
-    }
+// what a token does to the pileup (the effects policy of cs_walk, mpc_cswalk_host.h):
+// row is the sample's first row (u32[L + 1][4]), the counts are the record's
+struct RowFx {
+  uint32_t* row;
+  uint64_t n_match = 0, mism = 0, insev = 0, insb = 0, delev = 0, delb = 0;
+  void match(int64_t p, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) ++row[(p + i) * 4 + 0];
+    n_match += (uint64_t)n;
   }
-  *end = p;
-  return oor ? MPC_COV_RANGE : MPC_COV_OK;
-}
+  void mismatch(int64_t p, uint8_t) { ++row[p * 4 + 0]; ++row[p * 4 + 2]; ++mism; }
+  void deletion(int64_t p, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) ++row[(p + i) * 4 + 1];
+    ++delev;
+    delb += (uint64_t)n;
+  }
+  void insertion(int64_t p, int64_t n) { ++row[p * 4 + 3]; ++insev; insb += (uint64_t)n; }
+};
 
 // ---------------------------------------------------------------- PAF ingest
 
@@ -223,15 +170,8 @@ int mpc_coverage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* t
   if (!pos_off || !region || !rows || !stats || !status || !cs_off || (n_records > 0 && (!cs || !tstart || !rec_sample)))
     return cfail("mpc_coverage_host: null pointer");
   const size_t S = (size_t)n_samples;
-  if (pos_off[0] != 0) return cfail("mpc_coverage_host: pos_off[0] != 0");
-  for (size_t s = 0; s < S; ++s) {
-    const int64_t L = pos_off[s + 1] - pos_off[s] - 1, lo = region[2 * s], hi = region[2 * s + 1];
-    if (L < 0) return cfail("mpc_coverage_host: sample " + std::to_string(s) + ": pos_off is not increasing");
-    if (pos_off[s + 1] > INT32_MAX) return cfail("mpc_coverage_host: sample " + std::to_string(s) + ": n_pos is not below 2^31");
-    if (lo < 0 || lo > hi || hi > L)
-      return cfail("mpc_coverage_host: sample " + std::to_string(s) + ": region [" + std::to_string(lo) + ", " +
-                   std::to_string(hi) + ") is outside [0, " + std::to_string(L) + ")");
-  }
+  const std::string bad = mpc_host::check_samples(pos_off, region, S);
+  if (!bad.empty()) return cfail("mpc_coverage_host: " + bad);
   const size_t n_words = (size_t)pos_off[S] * 4;
   std::fill(rows, rows + n_words, 0u);
   std::fill(stats, stats + S * MPC_COV_STATS, (uint64_t)0);
@@ -243,9 +183,7 @@ int mpc_coverage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* t
   T = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)T, n_records, (int64_t)((1ull << 30) / (n_words * 4 + 1)) + 1}));
   std::vector<std::vector<uint32_t>> priv((size_t)T);
   std::vector<std::vector<uint64_t>> pstat((size_t)T);
-  std::vector<int64_t> first_bad((size_t)T, INT64_MAX);
-  std::vector<int> first_code((size_t)T, 0);
-  parallel(T, [&](int k) {
+  mpc_host::walk_records(n_records, T, status, [&](int k) {
     uint32_t* my = rows;
     if (k > 0) {
       priv[(size_t)k].assign(n_words, 0u);
@@ -253,35 +191,26 @@ int mpc_coverage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* t
     }
     pstat[(size_t)k].assign(S * 7, 0);
     uint64_t* ps = pstat[(size_t)k].data();
-    const int64_t a = n_records * k / T, b = n_records * (k + 1) / T;
-    for (int64_t r = a; r < b; ++r) {
+    return [=](int64_t r) {
       const int32_t s = rec_sample[r];
-      int code = MPC_COV_RANGE;
-      RecCounts rc;
+      if (s < 0 || s >= n_samples) return (int)MPC_COV_RANGE;
+      RowFx fx = {my + pos_off[s] * 4};
       int64_t end = 0;
-      if (s >= 0 && s < n_samples)
-        code = walk(cs + cs_off[r], cs_off[r + 1] - cs_off[r], tstart[r], pos_off[s + 1] - pos_off[s] - 1,
-                    my + pos_off[s] * 4, &rc, &end);
-      if (code != MPC_COV_OK) {
-        if (first_bad[(size_t)k] == INT64_MAX) { first_bad[(size_t)k] = r; first_code[(size_t)k] = code; }
-        continue;
-      }
+      const int code = mpc_host::cs_walk(cs + cs_off[r], cs_off[r + 1] - cs_off[r], tstart[r],
+                                         pos_off[s + 1] - pos_off[s] - 1, fx, &end);
+      if (code != MPC_COV_OK) return code;
       uint64_t* st = ps + (size_t)s * 7;
-      st[0] += 1; st[1] += rc.match; st[2] += rc.mism; st[3] += rc.insev; st[4] += rc.insb; st[5] += rc.delev; st[6] += rc.delb;
+      st[0] += 1; st[1] += fx.n_match; st[2] += fx.mism; st[3] += fx.insev; st[4] += fx.insb; st[5] += fx.delev; st[6] += fx.delb;
       if (rec_out) {
         rec_out[2 * r] = end;
-        rec_out[2 * r + 1] = (int64_t)(rc.match + rc.mism + rc.insb);
+        rec_out[2 * r + 1] = (int64_t)(fx.n_match + fx.mism + fx.insb);
       }
-    }
+      return (int)MPC_COV_OK;
+    };
   });
-  for (int k = 0; k < T; ++k) {
-    if (first_bad[(size_t)k] != INT64_MAX && status[0] == 0) {  // (cuts are in record order)
-      status[0] = first_code[(size_t)k];
-      status[1] = (int32_t)first_bad[(size_t)k];
-    }
+  for (int k = 0; k < T; ++k)
     for (size_t s = 0; s < S; ++s)
       for (int j = 0; j < 7; ++j) stats[s * MPC_COV_STATS + j] += pstat[(size_t)k][s * 7 + j];
-  }
   if (T > 1)
     parallel(T, [&](int k) {
       const size_t a = n_words * (size_t)k / T, b = n_words * (size_t)(k + 1) / T;

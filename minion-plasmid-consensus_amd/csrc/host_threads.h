@@ -1,9 +1,12 @@
-// host_threads.h -- default worker-thread count of the host-side libraries.
+// host_threads.h -- default worker-thread count of the host-side libraries,
+// and the fork-join they all use.
 #pragma once
 #include <sched.h>
 
+#include <cstddef>
 #include <cstdlib>
 #include <thread>
+#include <vector>
 
 namespace mpc_host {
 // OMP_NUM_THREADS when set (the GPU pool sets it to the job's CPU share), else
@@ -18,5 +21,15 @@ inline int host_threads() {
   if (sched_getaffinity(0, sizeof(cs), &cs) == 0 && CPU_COUNT(&cs) > 0) return CPU_COUNT(&cs);
   const unsigned hw = std::thread::hardware_concurrency();
   return hw ? (int)hw : 4;
+}
+
+// f(0) ... f(T - 1), one thread each (T <= 1: f(0) on the caller's), joined on return
+template <class F>
+void parallel(int T, F f) {
+  if (T <= 1) { f(0); return; }
+  std::vector<std::thread> th;
+  th.reserve((size_t)T);
+  for (int k = 0; k < T; ++k) th.emplace_back(f, k);
+  for (auto& t : th) t.join();
 }
 }  // namespace mpc_host

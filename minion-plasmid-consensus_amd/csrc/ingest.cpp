@@ -82,6 +82,7 @@ inline sv rstrip(sv s) {
 inline char upper(char c) { return (c >= 'a' && c <= 'z') ? (char)(c - 32) : c; }
 
 using mpc_host::host_threads;
+using mpc_host::parallel;
 
 // MPC_INGEST_TIMING=1: wall time of each ingest phase on stderr (a measurement
 // aid; called from the launching thread only).  phase(nullptr) starts the clock.
@@ -92,15 +93,6 @@ void phase(const char* what) {
   const auto t = std::chrono::steady_clock::now();
   if (what) fprintf(stderr, "ingest %-16s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - prev).count());
   prev = t;
-}
-
-template <class F>
-void parallel(int T, F f) {
-  if (T <= 1) { f(0); return; }
-  std::vector<std::thread> th;
-  th.reserve(T);
-  for (int k = 0; k < T; ++k) th.emplace_back(f, k);
-  for (auto& t : th) t.join();
 }
 
 // bytes Python decodes or translates in text mode: anything >= 0x80, '\r'

@@ -8,11 +8,12 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "host_threads.h"
 #include "mpc_coverage.h"
+#include "mpc_cstables.h"
+#include "mpc_cswalk_host.h"
 #include "mpc_linkage.h"
 
 namespace {
@@ -25,17 +26,7 @@ int lfail(const std::string& msg) {
   return kArg;
 }
 
-template <class F>
-void parallel(int T, F f) {
-  if (T <= 1) { f(0); return; }
-  std::vector<std::thread> th;
-  th.reserve((size_t)T);
-  for (int k = 0; k < T; ++k) th.emplace_back(f, k);
-  for (auto& t : th) t.join();
-}
-
-inline bool is_letter(uint8_t c) { return (uint8_t)((c | 32) - 'a') < 26; }
-inline bool is_digit(uint8_t c) { return (uint8_t)(c - '0') < 10; }
+using mpc_host::parallel;
 
 inline uint8_t sub_code(uint8_t y) {
   switch (y | 32) {
@@ -47,65 +38,33 @@ inline uint8_t sub_code(uint8_t y) {
   return 6;
 }
 
-// One record, straight from the definition.  key[0, nk): the sample's site
-// keys, row[0, nk): its allele codes (zero on entry).  Returns MPC_COV_*;
-// malformed wins over out of range, so the grammar is followed to the end of
-// the cs even once p has left the target.
-int walk(const uint8_t* q, int64_t len, int64_t ts, int64_t L, const int64_t* key, int64_t nk, uint8_t* row) {
-  if (len < 0) return MPC_COV_MALFORMED;
-  if (len >= 2 && q[0] == 'Z' && q[1] == ':') { q += 2; len -= 2; }
-  bool oor = ts < 0 || ts > L;
-  int64_t p = ts, k = 0;
-  auto mark = [&](int64_t want, uint8_t code) {
+// what a token does to the record's allele row (the effects policy of cs_walk,
+// mpc_cswalk_host.h).  key[0, nk): the sample's site keys, row[0, nk): its
+// allele codes (zero on entry)
+struct SiteFx {
+  const int64_t* key;
+  int64_t nk;
+  uint8_t* row;
+  void mark(int64_t want, uint8_t code) {
     const int64_t* it = std::lower_bound(key, key + nk, want);
     if (it != key + nk && *it == want) row[it - key] = code;
-  };
-  while (k < len) {
-    const uint8_t op = q[k++];
-    const int64_t a = k;
-    if (op == ':') {
-      int64_t n = 0;
-      while (k < len && is_digit(q[k])) {
-        if (k - a == 9) return MPC_COV_MALFORMED;  // a tenth digit
-        n = n * 10 + (q[k++] - '0');
-      }
-      if (k == a) return MPC_COV_MALFORMED;
-      if (!oor && p + n <= L) p += n;
-      else oor = true;
-    } else if (op == '*') {
-      if (len - k < 2 || !is_letter(q[k]) || !is_letter(q[k + 1])) return MPC_COV_MALFORMED;
-      k += 2;
-      if (k < len && is_letter(q[k])) return MPC_COV_MALFORMED;
-      if (!oor && p < L) {
-        mark(2 * p + 1, sub_code(q[k - 1]));
-        ++p;
-      } else oor = true;
-    } else if (op == '-' || op == '+') {
-      while (k < len && is_letter(q[k])) ++k;
-      const int64_t n = k - a;
-      if (n == 0) return MPC_COV_MALFORMED;
-      if (op == '-') {
-        if (!oor && p + n <= L) {
-          for (const int64_t* it = std::lower_bound(key, key + nk, 2 * p + 1); it != key + nk && *it < 2 * (p + n); ++it)
-            if (*it & 1) row[it - key] = 7;
-          p += n;
-        } else oor = true;
-      } else {
-        if (!oor && p <= L) mark(2 * p, 7);
-        else oor = true;
-      }
-    } else {
-      return MPC_COV_MALFORMED;
+  }
+  void match(int64_t, int64_t) {}
+  void mismatch(int64_t p, uint8_t y) { mark(2 * p + 1, sub_code(y)); }
+  void deletion(int64_t p, int64_t n) {
+    for (const int64_t* it = std::lower_bound(key, key + nk, 2 * p + 1); it != key + nk && *it < 2 * (p + n); ++it)
+      if (*it & 1) row[it - key] = 7;
+  }
+  void insertion(int64_t p, int64_t) { mark(2 * p, 7); }
+  // after a walk of [ts, end] that returned MPC_COV_OK: covered ? max(code, 1) : 0
+  void finish(int64_t ts, int64_t end) {
+    for (int64_t i = 0; i < nk; ++i) {
+      const int64_t s = key[i] >> 1;
+      const bool covered = s >= ts && ((key[i] & 1) ? s < end : s <= end);
+      row[i] = covered ? std::max<uint8_t>(row[i], 1) : 0;
     }
   }
-  if (oor) return MPC_COV_RANGE;
-  for (int64_t i = 0; i < nk; ++i) {
-    const int64_t s = key[i] >> 1;
-    const bool covered = s >= ts && ((key[i] & 1) ? s < p : s <= p);
-    row[i] = covered ? std::max<uint8_t>(row[i], 1) : 0;
-  }
-  return MPC_COV_OK;
-}
+};
 
 // pair[i][j][a][b] over the records: every thread counts the upper triangle of
 // its cut of the records into a table of its own, then the tables are summed
@@ -168,47 +127,25 @@ int mpc_linkage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* ts
     return lfail(fn + "null pointer");
   const size_t S = (size_t)n_samples;
   const int64_t K = n_sites;
-  if (pos_off[0] != 0) return lfail(fn + "pos_off[0] != 0");
-  if (site_off[0] != 0 || site_off[S] != K) return lfail(fn + "site_off does not run from 0 to n_sites");
-  for (size_t s = 0; s < S; ++s) {
-    const int64_t L = pos_off[s + 1] - pos_off[s] - 1;
-    const std::string who = fn + "sample " + std::to_string(s) + ": ";
-    if (L < 0) return lfail(who + "pos_off is not increasing");
-    if (pos_off[s + 1] > INT32_MAX) return lfail(who + "n_pos is not below 2^31");
-    if (site_off[s + 1] < site_off[s] || site_off[s + 1] > K) return lfail(who + "site_off is not monotone");
-    for (int64_t k = site_off[s]; k < site_off[s + 1]; ++k) {
-      const int64_t key = site_key[k];
-      if (key < 0 || key > 2 * L || ((key & 1) && key > 2 * L - 1))
-        return lfail(who + "site key " + std::to_string(key) + " is outside a target of " + std::to_string(L) + " bases");
-      if (k > site_off[s] && key <= site_key[k - 1]) return lfail(who + "site keys are not strictly increasing");
-    }
-  }
+  const std::string bad = mpc_host::check_sites(pos_off, site_off, site_key, S, K);
+  if (!bad.empty()) return lfail(fn + bad);
   status[0] = status[1] = 0;
   if (n_records > 0) std::memset(alleles, 0, (size_t)n_records * (size_t)K);
 
   int T = threads > 0 ? threads : mpc_host::host_threads();
   T = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)T, n_records));
-  std::vector<int64_t> first_bad((size_t)T, INT64_MAX);
-  std::vector<int> first_code((size_t)T, 0);
-  parallel(T, [&](int t) {
-    const int64_t a = n_records * t / T, b = n_records * (t + 1) / T;
-    for (int64_t r = a; r < b; ++r) {
+  mpc_host::walk_records(n_records, T, status, [&](int) {
+    return [=](int64_t r) {
       const int32_t s = rec_sample[r];
-      int code = MPC_COV_RANGE;
-      if (s >= 0 && s < n_samples)
-        code = walk(cs + cs_off[r], cs_off[r + 1] - cs_off[r], tstart[r], pos_off[s + 1] - pos_off[s] - 1,
-                    site_key + site_off[s], site_off[s + 1] - site_off[s], alleles + r * K + site_off[s]);
-      if (code != MPC_COV_OK && first_bad[(size_t)t] == INT64_MAX) {
-        first_bad[(size_t)t] = r;
-        first_code[(size_t)t] = code;
-      }
-    }
+      if (s < 0 || s >= n_samples) return (int)MPC_COV_RANGE;
+      SiteFx fx = {site_key + site_off[s], site_off[s + 1] - site_off[s], alleles + r * K + site_off[s]};
+      const int64_t ts = tstart[r];
+      int64_t end = 0;
+      const int code = mpc_host::cs_walk(cs + cs_off[r], cs_off[r + 1] - cs_off[r], ts, pos_off[s + 1] - pos_off[s] - 1, fx, &end);
+      if (code == MPC_COV_OK) fx.finish(ts, end);
+      return code;
+    };
   });
-  for (int t = 0; t < T; ++t)
-    if (first_bad[(size_t)t] != INT64_MAX && status[0] == 0) {  // (cuts are in record order)
-      status[0] = first_code[(size_t)t];
-      status[1] = (int32_t)first_bad[(size_t)t];
-    }
   count_pairs(alleles, n_records, n_sites, pair, threads);
   return kOk;
 }

@@ -27,6 +27,7 @@
 
 #include "mpc.h"
 #include "mpc_coverage.h"
+#include "mpc_cstables.h"
 #include "mpc_cswalk.h"
 #include "mpc_device.h"
 
@@ -338,15 +339,8 @@ extern "C" int mpc_coverage_run(const uint8_t* d_cs, const int64_t* d_cs_off, co
   if (e == hipSuccess) e = hipMemcpyAsync(h.data() + S + 1, d_region, 2 * S * sizeof(int64_t), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return hip_fail("sample tables", e);
-  if (h[0] != 0) return mpc_fail_(MPC_E_ARG, "mpc_coverage_run: pos_off[0] != 0");
-  for (size_t s = 0; s < S; ++s) {
-    const int64_t L = h[s + 1] - h[s] - 1, lo = h[S + 1 + 2 * s], hi = h[S + 2 + 2 * s];
-    std::string bad;
-    if (L < 0) bad = "pos_off is not increasing";
-    else if (h[s + 1] > INT32_MAX) bad = "n_pos is not below 2^31";
-    else if (lo < 0 || lo > hi || hi > L) bad = "region [" + std::to_string(lo) + ", " + std::to_string(hi) + ") is outside [0, " + std::to_string(L) + ")";
-    if (!bad.empty()) return mpc_fail_(MPC_E_ARG, ("mpc_coverage_run: sample " + std::to_string(s) + ": " + bad).c_str());
-  }
+  const std::string bad = mpc_host::check_samples(h.data(), h.data() + S + 1, S);
+  if (!bad.empty()) return mpc_fail_(MPC_E_ARG, ("mpc_coverage_run: " + bad).c_str());
   const int64_t n_pos = h[S];
   e = hipMemsetAsync(d_rows, 0, (size_t)n_pos * 4 * sizeof(uint32_t), st);
   if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, S * MPC_COV_STATS * sizeof(uint64_t), st);

@@ -16,6 +16,7 @@
 
 #include "mpc.h"
 #include "mpc_coverage.h"
+#include "mpc_cstables.h"
 #include "mpc_cswalk.h"
 #include "mpc_device.h"
 #include "mpc_linkage.h"
@@ -358,21 +359,8 @@ extern "C" int mpc_linkage_run(const uint8_t* d_cs, const int64_t* d_cs_off, con
   if (e == hipSuccess) e = hipMemcpyAsync(key, d_site_key, K * sizeof(int64_t), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return lnk_hip_fail(fn, "sample and site tables", e);
-  if (pos[0] != 0) return lnk_fail(fn, "pos_off[0] != 0");
-  if (off[0] != 0 || off[S] != (int64_t)K) return lnk_fail(fn, "site_off does not run from 0 to n_sites");
-  for (size_t s = 0; s < S; ++s) {
-    const int64_t L = pos[s + 1] - pos[s] - 1;
-    std::string bad;
-    if (L < 0) bad = "pos_off is not increasing";
-    else if (pos[s + 1] > INT32_MAX) bad = "n_pos is not below 2^31";
-    else if (off[s + 1] < off[s] || off[s + 1] > (int64_t)K) bad = "site_off is not monotone";
-    for (int64_t k = off[s]; bad.empty() && k < off[s + 1]; ++k) {
-      if (key[k] < 0 || key[k] > 2 * L || ((key[k] & 1) && key[k] > 2 * L - 1))
-        bad = "site key " + std::to_string(key[k]) + " is outside a target of " + std::to_string(L) + " bases";
-      else if (k > off[s] && key[k] <= key[k - 1]) bad = "site keys are not strictly increasing";
-    }
-    if (!bad.empty()) return lnk_fail(fn, "sample " + std::to_string(s) + ": " + bad);
-  }
+  const std::string bad = mpc_host::check_sites(pos, off, key, S, (int64_t)K);
+  if (!bad.empty()) return lnk_fail(fn, bad);
   e = hipMemsetAsync(d_scratch, 0, kPlaneHead, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, 2 * sizeof(int32_t), st);
   if (e != hipSuccess) return lnk_hip_fail(fn, "clearing the status", e);

@@ -108,29 +108,12 @@ def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, t
     at the sites site_off[S + 1] / site_key[K] (2p + 1: base p, 2p: the gap before
     base p).  Raises LinkageError naming the smallest malformed or out-of-range
     record, or what is wrong with the tables."""
-    cs = np.ascontiguousarray(cs, np.uint8)
-    cs_off = np.ascontiguousarray(cs_off, np.int64)
-    tstart = np.ascontiguousarray(tstart, np.int64)
-    rec_sample = np.ascontiguousarray(rec_sample, np.int32)
     site_off = np.ascontiguousarray(site_off, np.int64)
     site_key = np.ascontiguousarray(site_key, np.int64)
     n, S, K = len(tstart), len(lengths), len(site_key)
-    if len(cs_off) != n + 1 or len(rec_sample) != n:
-        raise LinkageError("cs_off, tstart and rec_sample disagree on the number of records")
-    if S < 1:
-        raise LinkageError("no target")
-    if len(site_off) != S + 1:
-        raise LinkageError("site_off needs one entry per target and one more")
-    if not 1 <= K <= MAX_SITES:
-        raise LinkageError("{} sites: outside [1, {}]".format(K, MAX_SITES))
-    if n and (cs_off[0] < 0 or (np.diff(cs_off) < 0).any() or cs_off[-1] > len(cs)):
-        raise LinkageError("cs_off does not cut the cs bytes")
-    if n and (rec_sample.min() < 0 or rec_sample.max() >= S):
-        raise LinkageError("a record names a target outside [0, {})".format(S))
-    pos_off = np.zeros(S + 1, np.int64)
-    pos_off[1:] = np.cumsum(np.asarray(lengths, np.int64) + 1)
-    if min(lengths) < 0 or pos_off[-1] >= 2 ** 31:
-        raise LinkageError("target lengths must be >= 0 and sum (with one extra row each) to below 2^31")
+    more = [(len(site_off) != S + 1, "site_off needs one entry per target and one more"),
+            (not 1 <= K <= MAX_SITES, "{} sites: outside [1, {}]".format(K, MAX_SITES))]
+    cs, cs_off, tstart, rec_sample, pos_off = coverage.batch_front(LinkageError, cs, cs_off, tstart, rec_sample, lengths, more)
     if device == "cpu":
         L = host_lib()
         alleles = np.zeros((n, K), np.uint8)
@@ -143,18 +126,13 @@ def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, t
     else:
         L = _device_lib()
         torch, dev = _torch_device(device)
-        # one blob, one H2D copy: the int64 tables first (8-byte aligned), then rec_sample, then the cs bytes
-        parts = [cs_off, tstart, pos_off, site_off, site_key, rec_sample, cs, np.zeros(8, np.uint8)]
-        offs = np.cumsum([0] + [p.nbytes for p in parts])
-        blob = np.concatenate([p.view(np.uint8).reshape(-1) for p in parts])
         with torch.cuda.device(dev):
-            d_blob = torch.empty(len(blob), dtype=torch.uint8, device=dev)
-            d_blob.copy_(torch.from_numpy(blob))
+            # the int64 tables first, then rec_sample, then the cs bytes
+            at, d_blob = coverage.upload(torch, dev, [cs_off, tstart, pos_off, site_off, site_key, rec_sample, cs])
             d_alleles = torch.empty((n, K), dtype=torch.uint8, device=dev)
             d_pair = torch.empty((K, K, CODES, CODES), dtype=torch.int32, device=dev)
             d_scratch = torch.empty(max(8, L.mpc_linkage_scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            at = [d_blob.data_ptr() + int(o) for o in offs]
             stream = torch.cuda.current_stream(dev)
             _device_check(L, L.mpc_linkage_run(at[6], at[0], at[1], at[5], n, at[2], S, at[3], at[4], K,
                                                d_alleles.data_ptr(), d_pair.data_ptr(), d_scratch.data_ptr(),
@@ -162,8 +140,7 @@ def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, t
             status = d_status.cpu().numpy()
             alleles = d_alleles.cpu().numpy()
             pair = d_pair.cpu().numpy().view(np.uint32)
-    if status[0] != 0:
-        raise LinkageError("record {}: {}".format(int(status[1]), coverage.CODES.get(int(status[0]), "code %d" % status[0])))
+    coverage.raise_status(LinkageError, status)
     return alleles, pair
 
 

@@ -157,6 +157,62 @@ def synth_batch(pkg):
     return records, lengths, regions, samples
 
 
+def bad_sample_batch():
+    """(records, lengths, bad): 2 x 16 x 64 + 17 records of 2-6-byte cs strings
+    over two 40-base targets -- two full rounds of a 16-wave workgroup's
+    64-record batches and a short third; record 1024 (lane 0 of a batch) and the
+    last record are to be given a sample index outside the targets."""
+    rng = np.random.default_rng(61)
+    toks = (b":1", b"*ag", b"-a", b"+c", b":3", b"*ct:2", b":2-ac", b"+gt:1", b"-acg:1")
+    n = 2 * 16 * 64 + 17
+    records = [(int(rng.integers(0, 2)), int(rng.integers(0, 34)), toks[int(rng.integers(0, len(toks)))]) for _ in range(n)]
+    return records, [40, 40], (1024, n - 1)
+
+
+def run_abi(pkg, packed, pos_off, region, device):
+    """mpc_coverage_host / mpc_coverage_run on arrays as they are (coverage.run
+    refuses a sample index outside the targets before either): (status, rows, stats)."""
+    cs, off, ts, rs = packed
+    n, S, n_pos = len(ts), len(pos_off) - 1, int(pos_off[-1])
+    if device == "cpu":
+        L = pkg.coverage.host_lib()
+        rows, stats, status = np.zeros((n_pos, 4), np.uint32), np.zeros((S, 16), np.uint64), np.zeros(2, np.int32)
+        cs = np.concatenate([cs, np.zeros(8, np.uint8)])
+        rc = L.mpc_coverage_host(cs.ctypes.data, off.ctypes.data, ts.ctypes.data, rs.ctypes.data, n, pos_off.ctypes.data,
+                                 region.ctypes.data, S, 0, rows.ctypes.data, stats.ctypes.data, status.ctypes.data, 3, None)
+        assert rc == 0, L.mpc_coverage_last_error()
+        return tuple(status.tolist()), rows, stats
+    import torch
+    L = pkg.coverage._device_lib()
+    dev = "cuda:%d" % device
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_cs, d_off, d_ts, d_rs, d_pos, d_reg = (up(a) for a in (np.concatenate([cs, np.zeros(8, np.uint8)]), off, ts, rs,
+                                                             pos_off, region))
+    d_rows = torch.empty((n_pos, 4), dtype=torch.int32, device=dev)
+    d_stats = torch.empty((S, 16), dtype=torch.int64, device=dev)
+    d_status = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mpc_coverage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(), n, d_pos.data_ptr(),
+                                d_reg.data_ptr(), S, 0, d_rows.data_ptr(), d_stats.data_ptr(), d_status.data_ptr(), None)
+        assert rc == 0, L.mpc_last_error()
+        torch.cuda.synchronize()
+    return tuple(d_status.cpu().tolist()), d_rows.cpu().numpy().view(np.uint32), d_stats.cpu().numpy().view(np.uint64)
+
+
+def case_bad_sample(pkg, device):
+    """A sample index outside the targets in lane 0 of a wave's batch and in the
+    last record: the smaller one is named, out of range; every other record counts."""
+    records, lengths, bad = bad_sample_batch()
+    regions = [(0, L) for L in lengths]
+    _, rows, stats, _ = check([r for k, r in enumerate(records) if k not in bad], lengths, regions)
+    packed = pack(records)
+    packed[3][bad[0]], packed[3][bad[1]] = len(lengths), -1
+    pos_off = np.concatenate([[0], np.cumsum(np.asarray(lengths, np.int64) + 1)]).astype(np.int64)
+    got = run_abi(pkg, packed, pos_off, np.array(regions, np.int64).reshape(-1), device)
+    assert got[0] == (RANGE, bad[0])
+    assert np.array_equal(got[1], rows) and np.array_equal(got[2], stats)
+
+
 MALFORMED_CS = {  # one per grammar rule of the issue
     "tenth_digit": b":1234567890",
     "space_in_number": b": 7",

@@ -444,6 +444,57 @@ def case_status_far_apart(pkg, device):
     assert status_of(pkg, batch, [20], device) == cu.status_of(pkg, batch, [20], device) == (cu.MALFORMED, 50)
 
 
+def run_abi(pkg, packed, pos_off, site_off, site_key, device):
+    """mpc_linkage_host / mpc_linkage_run on arrays as they are (linkage.run
+    refuses a sample index outside the targets before either): (status, alleles, pair)."""
+    cs, off, ts, rs = packed
+    n, S, K = len(ts), len(pos_off) - 1, len(site_key)
+    cs = np.concatenate([cs, np.zeros(8, np.uint8)])
+    if device == "cpu":
+        L = pkg.linkage.host_lib()
+        alleles, pair, status = np.full((n, K), 9, np.uint8), np.zeros((K, K, 8, 8), np.uint32), np.zeros(2, np.int32)
+        rc = L.mpc_linkage_host(cs.ctypes.data, off.ctypes.data, ts.ctypes.data, rs.ctypes.data, n, pos_off.ctypes.data, S,
+                                site_off.ctypes.data, site_key.ctypes.data, K, alleles.ctypes.data, pair.ctypes.data,
+                                status.ctypes.data, 3)
+        assert rc == 0, L.mpc_linkage_last_error()
+        return tuple(status.tolist()), alleles, pair
+    import torch
+    L = pkg.linkage._device_lib()
+    dev = "cuda:%d" % device
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_cs, d_off, d_ts, d_rs, d_pos, d_so, d_sk = (up(a) for a in (cs, off, ts, rs, pos_off, site_off, site_key))
+    d_alleles = torch.full((n, K), 9, dtype=torch.uint8, device=dev)
+    d_pair = torch.empty((K, K, 8, 8), dtype=torch.int32, device=dev)
+    d_scratch = torch.empty(L.mpc_linkage_scratch_bytes(n, K) // 8, dtype=torch.int64, device=dev)
+    d_status = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mpc_linkage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(), n, d_pos.data_ptr(), S,
+                               d_so.data_ptr(), d_sk.data_ptr(), K, d_alleles.data_ptr(), d_pair.data_ptr(),
+                               d_scratch.data_ptr(), d_status.data_ptr(), None)
+        assert rc == 0, L.mpc_last_error()
+        torch.cuda.synchronize()
+    return tuple(d_status.cpu().tolist()), d_alleles.cpu().numpy(), d_pair.cpu().numpy().view(np.uint32)
+
+
+def case_bad_sample(pkg, device):
+    """cov_util.bad_sample_batch: the smaller record with a sample index outside
+    the targets is named, out of range; both have an all-zero allele row and
+    every other record its codes."""
+    records, lengths, bad = cu.bad_sample_batch()
+    off, key = tables([[base(3), gap(4), base(17), gap(40)], [gap(0), base(5), gap(18), base(30), base(39)]])
+    good = [k for k in range(len(records)) if k not in bad]
+    status, want, _ = check([records[k] for k in good], lengths, off, key)
+    assert status == (cu.OK, 0) and (want >= 2).any() and (want == 1).any() and (want == 0).any()
+    alleles = np.zeros((len(records), len(key)), np.uint8)
+    alleles[good] = want
+    packed = cu.pack(records)
+    packed[3][bad[0]], packed[3][bad[1]] = -7, len(lengths)
+    pos_off = np.concatenate([[0], np.cumsum(np.asarray(lengths, np.int64) + 1)]).astype(np.int64)
+    got = run_abi(pkg, packed, pos_off, off, key, device)
+    assert got[0] == (cu.RANGE, bad[0])
+    assert np.array_equal(got[1], alleles) and np.array_equal(got[2], pair_of(alleles))
+
+
 # (site_off, site_key, n_sites, word of the message) on two targets of 10 and 6 bases
 BAD_TABLES = [
     ([0, 2, 3], [5, 5, 4], 3, b"increasing"), ([0, 2, 3], [7, 5, 4], 3, b"increasing"),

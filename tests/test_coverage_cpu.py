@@ -98,6 +98,10 @@ def test_smaller_bad_index_wins(pkg):
     assert cu.status_of(pkg, batch, [20]) == (cu.MALFORMED, 4)
 
 
+def test_sample_index_outside_the_targets(pkg):
+    cu.case_bad_sample(pkg, "cpu")
+
+
 def test_abi_argument_checks(pkg):
     L = pkg.coverage.host_lib()
     z = np.zeros(64, np.int64)

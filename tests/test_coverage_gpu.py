@@ -172,6 +172,10 @@ def test_status_smaller_index_wins_far_apart(pkg, tile):
     assert cu.status_of(pkg, batch, [20], device=0) == (cu.MALFORMED, 50)
 
 
+def test_sample_index_outside_the_targets(pkg):
+    cu.case_bad_sample(pkg, 0)
+
+
 def test_run_refuses_bad_tables_before_launch(pkg):
     import torch
     L = pkg.coverage._device_lib()

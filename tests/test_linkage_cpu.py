@@ -53,6 +53,10 @@ def test_status_smaller_index_wins_far_apart(pkg):
     lu.case_status_far_apart(pkg, DEV)
 
 
+def test_sample_index_outside_the_targets(pkg):
+    lu.case_bad_sample(pkg, DEV)
+
+
 def test_host_refuses_bad_tables_untouched(pkg):
     L = pkg.linkage.host_lib()
     cs = np.frombuffer(b":3" + b"\0" * 6, np.uint8)

@@ -73,6 +73,10 @@ def test_status_smaller_index_wins_far_apart(pkg):
     lu.case_status_far_apart(pkg, DEV)
 
 
+def test_sample_index_outside_the_targets(pkg):
+    lu.case_bad_sample(pkg, DEV)
+
+
 def test_run_refuses_bad_tables_before_launch(pkg):
     import torch
     L = pkg.linkage._device_lib()
