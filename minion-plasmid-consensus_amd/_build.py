@@ -22,7 +22,11 @@ LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 
 HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip", "mpc_link.hip"]
 HOST_SOURCES = ["mpc_plan.cpp"]  # libmpc.so's host planner (g++, no HIP)
-HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h", "mpc_cstables.h"]
+HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h", "mpc_cstables.h",
+               # the stages of mpc_kernels.hip (one translation unit), in pipeline order
+               "mpc_k_common.h", "mpc_k_parse.h", "mpc_k_index.h", "mpc_k_left.h", "mpc_k_wrap.h", "mpc_k_layout.h",
+               "mpc_k_rows.h", "mpc_k_call.h"]
+INGEST_SOURCES = ["ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp"]
 INGEST_HEADERS = ["host_threads.h", "mpc_cswalk_host.h", "mpc_cstables.h"]  # csrc headers of libmpc_ingest.so
 
 
@@ -45,7 +49,7 @@ def ensure_synth():
 
 
 def build_ingest(force=False):
-    srcs = [os.path.join(CSRC, f) for f in ("ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in INGEST_SOURCES]
     hdrs = [os.path.join(INCLUDE, h) for h in ("mpc_ingest.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h")]
     if force or _stale(LIBINGEST, srcs + hdrs + [os.path.join(CSRC, h) for h in INGEST_HEADERS]):
         subprocess.run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I", INCLUDE, "-o", LIBINGEST] + srcs,

@@ -1,5 +1,5 @@
 // The contract between the host planner (mpc_plan.cpp) and the kernels
-// (mpc_kernels.hip): the constants, sizing functions and plain structs both
+// (mpc_k_*.h, compiled as mpc_kernels.hip): the constants, sizing functions and plain structs both
 // sides must agree on.  What a plan depends on is all here; the kernels keep
 // what only they use.  No HIP header: this compiles under plain g++ as well as
 // under hipcc.
@@ -18,7 +18,7 @@
 namespace mpc_geom {
 
 // 32-bit coordinates and the 22-bit gap of the insertion event word bound the
-// reference (mpc_kernels.hip: kAdvCap, kNullGap)
+// reference (mpc_k_common.h: kAdvCap, kNullGap)
 constexpr int kMaxRefLen = (1 << 22) - 2;
 constexpr int kBW = 64;             // gaps per insertion bucket (K_left workgroup)
 static_assert(kBW <= 64 && (kBW & (kBW - 1)) == 0, "sorted insertion events hold the gap within its bucket in 6 bits");

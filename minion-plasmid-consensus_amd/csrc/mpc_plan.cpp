@@ -1,8 +1,8 @@
 // libmpc's host planner: every C-ABI entry point (include/mpc.h) that touches
 // no device.  mpc_plan_create turns the shape of an input into the parse
 // geometry, the work tables and the workspace layout the phases of
-// mpc_kernels.hip launch from.  Plain C++ (no HIP): what it shares with the
-// kernels is mpc_geometry.h.
+// mpc_kernels.hip launch from (the kernels and their launchers: mpc_k_*.h).
+// Plain C++ (no HIP): what it shares with the kernels is mpc_geometry.h.
 #include "mpc_plan.h"
 
 #include <algorithm>

@@ -1,6 +1,6 @@
 // The plan behind the C-ABI's mpc_plan handle (include/mpc.h): what the host
-// planner (mpc_plan.cpp, no HIP) decides and the phases (mpc_kernels.hip)
-// launch from.
+// planner (mpc_plan.cpp, no HIP) decides and the phases (mpc_kernels.hip, with
+// the argument fillers and launchers of the mpc_k_*.h stage headers) launch from.
 #pragma once
 
 #include <cstddef>

@@ -75,7 +75,7 @@ def test_planner_geometry(pkg):
 
 
 def test_planner_deferred_placement(pkg):
-    """K_parse queues insertion events per wave in LDS (mpc_kernels.hip
+    """K_parse queues insertion events per wave in LDS (mpc_k_parse.h
     K_parse DP; mpc_geometry.h kDefQ; planned in mpc_plan.cpp) only with 2 KiB windows in tally mode 1 or 3 with one
     substitution window, and only when the queues fit the LDS budget without
     changing the geometry: C2-C4 take it, C1 and C5 (LDS full) do not; reads
@@ -231,12 +231,16 @@ def test_one_hip_runtime_either_order(order):
 def test_product_build_flags(pkg):
     """The shipped libmpc.so is the product build: no stamps, no planner
     overrides, no kernel variant macro (the timing ablations
-    live in exp/ablations.patch, not in the product source)."""
+    live in exp/ablations.patch, not in any file libmpc.so is built from)."""
     lib = pkg.engine.lib()
     lib.mpc_build_flags.restype = ctypes.c_int
     assert lib.mpc_build_flags() == 0
-    src = open(os.path.join(REPO, "minion-plasmid-consensus_amd", "csrc", "mpc_kernels.hip")).read()
-    assert "MPC_ABL_" not in src and "wrong results" not in src
+    b = pkg._build
+    names = b.HIP_SOURCES + b.HOST_SOURCES + b.HIP_HEADERS
+    assert "mpc_kernels.hip" in names and "mpc_k_parse.h" in names
+    for name in names:
+        src = open(os.path.join(b.CSRC, name)).read()
+        assert "MPC_ABL_" not in src and "wrong results" not in src, name
 
 
 def test_hip_runtime_soname_check(pkg, monkeypatch):

@@ -16,7 +16,7 @@ import oracle
 pytestmark = pytest.mark.gpu
 
 KEYS = ("base", "chrom1", "chrom2", "count", "count2", "total")
-STAGE, SEG, GROUP = 2032, 256, 64  # csrc/mpc_kernels.hip: kFStage, kFSeg, bytes per group
+STAGE, SEG, GROUP = 2032, 256, 64  # csrc/mpc_k_rows.h: kFStage, kFSeg, bytes per group
 
 
 def _oracle(s, mdf=-1.0, gtf=1.0):

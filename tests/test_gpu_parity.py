@@ -384,7 +384,7 @@ def test_two_byte_substitutions_mode3(pkg):
 @pytest.mark.parametrize("mode,reads", [(1, 400), (3, 300), (1, 1), (3, 2)])
 def test_deferred_placement_dense_insertions(pkg, mode, reads):
     """Insertions queued per wave in LDS and placed 64 at a time
-    (mpc_kernels.hip K_parse DP; mpc_plan_info.deferred_placement): reads
+    (mpc_k_parse.h K_parse DP; mpc_plan_info.deferred_placement): reads
     of dense 1-4 base '+' tokens (every round fills the queue, bucket pages
     open during the flushes) plus longer ones (the overflow list, not queued),
     and single reads whose few events wait in the queue until the last flush."""
