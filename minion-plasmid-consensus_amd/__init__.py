@@ -10,15 +10,18 @@ Modules
   verify   exact alignment of consensus files with the expected plasmid (K_vscan)
   coverage per-position depth / deletion / mismatch / insertion profile from the PAF (K_covparse)
   linkage  per-read alleles at variable sites and their pairwise co-occurrence (K_lnkparse, K_lnkpair)
+  align    exact read-to-assembly alignment to a cs-tagged PAF (K_arevcomp, K_vscan, K_atrace)
   mapped_paf_read_parser  the drop-in CLI
   verify_consensus        the "Check the results" CLI
   coverage_qc             the coverage criterion CLI
   linkage_qc              the sub-population (linked minor alleles) CLI
+  align_reads             the final_alignment_paf CLI (reads + assembly -> PAF)
 """
 from . import _build, ingest, writers, synth  # noqa: F401
 from . import engine  # noqa: F401
 from . import verify  # noqa: F401
 from . import coverage  # noqa: F401
 from . import linkage  # noqa: F401
+from . import align  # noqa: F401
 
-__all__ = ["ingest", "engine", "writers", "synth", "verify", "coverage", "linkage"]
+__all__ = ["ingest", "engine", "writers", "synth", "verify", "coverage", "linkage", "align"]

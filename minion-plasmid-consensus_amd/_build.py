@@ -1,12 +1,13 @@
 """In-tree builds of the native libraries (no JIT cache: the .so files travel with
 the repo snapshot to the GPU box).
 
-  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan, mpc_coverage.h: K_covparse, mpc_linkage.h: K_lnkparse), hipcc --offload-arch=gfx950;
+  libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan, mpc_coverage.h: K_covparse, mpc_linkage.h: K_lnkparse,
+                   mpc_align.h: K_arevcomp, K_atrace), hipcc --offload-arch=gfx950;
                    its host planner (csrc/mpc_plan.cpp) with g++
   libmpc_synth.so  host-only synthetic data generator (g++)
   libmpc_ingest.so native host I/O: ingest (Steps 1-3) and writers (Step 7) (include/mpc_ingest.h, g++ -pthread)
                    and the host halves of verify_consensus (include/mpc_verify.h), coverage_qc (mpc_coverage.h)
-                   and linkage_qc (mpc_linkage.h)
+                   linkage_qc (mpc_linkage.h) and align_reads (mpc_align.h)
 """
 import os
 import subprocess
@@ -20,13 +21,13 @@ LIBMPC = os.path.join(PKG, "libmpc.so")
 LIBSYNTH = os.path.join(PKG, "libmpc_synth.so")
 LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 
-HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip", "mpc_link.hip"]
+HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip", "mpc_link.hip", "mpc_align.hip"]
 HOST_SOURCES = ["mpc_plan.cpp"]  # libmpc.so's host planner (g++, no HIP)
 HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h", "mpc_cstables.h",
                # the stages of mpc_kernels.hip (one translation unit), in pipeline order
                "mpc_k_common.h", "mpc_k_parse.h", "mpc_k_index.h", "mpc_k_left.h", "mpc_k_wrap.h", "mpc_k_layout.h",
                "mpc_k_rows.h", "mpc_k_call.h"]
-INGEST_SOURCES = ["ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp"]
+INGEST_SOURCES = ["ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp", "align.cpp"]
 INGEST_HEADERS = ["host_threads.h", "mpc_cswalk_host.h", "mpc_cstables.h"]  # csrc headers of libmpc_ingest.so
 
 
@@ -50,7 +51,7 @@ def ensure_synth():
 
 def build_ingest(force=False):
     srcs = [os.path.join(CSRC, f) for f in INGEST_SOURCES]
-    hdrs = [os.path.join(INCLUDE, h) for h in ("mpc_ingest.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h")]
+    hdrs = [os.path.join(INCLUDE, h) for h in ("mpc_ingest.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h", "mpc_align.h")]
     if force or _stale(LIBINGEST, srcs + hdrs + [os.path.join(CSRC, h) for h in INGEST_HEADERS]):
         subprocess.run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I", INCLUDE, "-o", LIBINGEST] + srcs,
                        check=True)
@@ -62,7 +63,7 @@ def build_hip(force=False, extra=(), out=None):
     out = out or LIBMPC
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     host = [os.path.join(CSRC, s) for s in HOST_SOURCES]
-    deps = srcs + host + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h")]
+    deps = srcs + host + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(INCLUDE, h) for h in ("mpc.h", "mpc_verify.h", "mpc_coverage.h", "mpc_linkage.h", "mpc_align.h")]
     if force or extra or _stale(out, deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         flags = ["-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC] + list(extra)

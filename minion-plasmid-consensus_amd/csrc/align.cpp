@@ -1,0 +1,383 @@
+// align.cpp -- host half of align_reads (include/mpc_align.h):
+//   mpc_align_revcomp_host  the minus-strand queries (--device cpu)
+//   mpc_align_plan          strand, mapped or not, band sizes, launch cuts
+//   mpc_align_trace_host    scalar band DP + canonical traceback + run encoding:
+//                           the CPU checker of K_atrace, the timing baseline,
+//                           --device cpu
+//   mpc_align_render        end rule + PAF lines of a batch
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "host_threads.h"
+#include "mpc_align.h"
+
+namespace {
+
+constexpr int kOk = 0, kArg = -1;  // MPC_OK, MPC_E_ARG of mpc.h
+
+thread_local std::string g_aerr;
+int afail(const std::string& msg, int code = kArg) {
+  g_aerr = msg;
+  return code;
+}
+
+// A C G T -> 0..3 after upper-casing; any other byte -> `other` (mpc_verify.h)
+inline uint8_t vcode(uint8_t c, uint8_t other) {
+  switch (c) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+  }
+  return other;
+}
+
+inline uint8_t complement(uint8_t c) {
+  switch (c) {
+    case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
+    case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
+  }
+  return c;
+}
+
+inline char lower(uint8_t c) { return (char)((c >= 'A' && c <= 'Z') ? c + 32 : c); }
+
+inline int64_t row_pitch(int64_t d) { return (2 * d + 1 + 63) / 64 * 64; }
+
+int clamp_threads(int threads, int64_t work) {
+  const int nt = threads > 0 ? threads : mpc_host::host_threads();
+  return (int)std::max<int64_t>(1, std::min<int64_t>(nt, work));
+}
+
+// what the host refuses before any read is traced (K_atrace's launch checks the same)
+const char* check_job(const int64_t* j, int64_t seq_bytes, int64_t runs_cap) {
+  const int64_t q_off = j[0], m = j[1], t_off = j[2], n = j[3], d = j[4], end = j[5], run_off = j[7];
+  if (m < 1 || m > MPC_VERIFY_MAX_QUERY) return "read length outside [1, MPC_VERIFY_MAX_QUERY]";
+  if (n < 1 || n > INT32_MAX) return "target length outside [1, 2^31)";
+  if (d < 0 || d > MPC_ALIGN_MAX_EDITS) return "distance outside [0, MPC_ALIGN_MAX_EDITS]";
+  if (end < 0 || end > n) return "end outside [0, n]";
+  if (q_off < 0 || q_off > seq_bytes - m || t_off < 0 || t_off > seq_bytes - n) return "sequence outside the blob";
+  if (run_off < 0 || run_off > runs_cap - (2 * d + 1)) return "runs outside the run buffer";
+  return nullptr;
+}
+
+enum : uint8_t { kDiag = 1, kUp = 2, kMatch = 4 };
+enum : int32_t { kOpEq = 0, kOpX = 1, kOpI = 2, kOpD = 3 };
+
+struct Band {  // one thread's scratch, grown as needed
+  std::vector<uint8_t> flags, tc;
+  std::vector<int32_t> row;
+};
+
+// One read: the definition's band DP (row i over slots b, one row of values kept
+// in place), the traceback from (m, end) and the runs, end -> start.
+void trace_one(const uint8_t* q, const uint8_t* t, const int64_t* job, int32_t* o, int32_t* runs, Band& s) {
+  const int64_t m = job[1], n = job[3], d = job[4], end = job[5];
+  const int64_t W = 2 * d + 1, P = row_pitch(d), d0 = end - m;
+  const int32_t INF = 1 << 20;
+  for (int k = 0; k < 8; ++k) o[k] = 0;
+  s.flags.resize((size_t)(m * P));
+  s.row.resize((size_t)W + 1);
+  // the target bytes any band cell can touch: columns [jlo, jhi]
+  const int64_t jlo = std::max<int64_t>(1, 1 + d0 - d), jhi = std::min<int64_t>(n, end + d);
+  s.tc.resize((size_t)std::max<int64_t>(0, jhi - jlo + 1));
+  for (int64_t j = jlo; j <= jhi; ++j) s.tc[(size_t)(j - jlo)] = vcode(t[j - 1], 5);
+  int32_t* row = s.row.data();
+  for (int64_t b = 0; b < W; ++b) {
+    const int64_t j = d0 - d + b;
+    row[b] = (j >= 0 && j <= n) ? 0 : INF;  // D[0][j] = 0
+  }
+  row[W] = INF;
+  for (int64_t i = 1; i <= m; ++i) {
+    const uint8_t qi = vcode(q[i - 1], 4);
+    uint8_t* f = &s.flags[(size_t)((i - 1) * P)];
+    int32_t left = INF;  // D[i][j - 1]
+    for (int64_t b = 0; b < W; ++b) {
+      const int64_t j = i + d0 - d + b;
+      int32_t v = INF;
+      uint8_t fl = 0;
+      if (j >= 0 && j <= n) {
+        // row i - 1: column j - 1 is slot b, column j is slot b + 1
+        const int32_t up = row[b + 1] + 1;
+        if (j == 0) {
+          v = (int32_t)i;
+          fl = kUp;
+        } else {
+          const bool eq = qi == s.tc[(size_t)(j - jlo)];
+          const int32_t dg = row[b] + (eq ? 0 : 1);
+          v = std::min(dg, std::min(up, left + 1));
+          if (dg == v) fl |= kDiag;
+          if (up == v) fl |= kUp;
+          if (eq) fl |= kMatch;
+        }
+        if (v > INF) v = INF;
+      }
+      row[b] = v;
+      left = v;
+      f[b] = fl;
+    }
+  }
+  if (row[d] != (int32_t)d) {  // (m, end) sits on diagonal d0: slot d
+    o[0] = MPC_ALIGN_BAD_SCAN;
+    return;
+  }
+  int64_t i = m, j = end;
+  int32_t cnt[4] = {0, 0, 0, 0}, n_runs = 0, op = -1, len = 0;
+  const int32_t cap = (int32_t)W;
+  bool bad = false;
+  auto flush = [&]() {
+    if (len > 0) {
+      if (n_runs < cap) runs[n_runs] = (len << 2) | op;
+      else bad = true;
+      ++n_runs;
+    }
+  };
+  while (i > 0) {
+    const int64_t b = j - i - d0 + d;
+    if (b < 0 || b >= W) { bad = true; break; }
+    const uint8_t fl = s.flags[(size_t)((i - 1) * P + b)];
+    int32_t now;
+    if (j > 0 && (fl & kDiag)) { now = (fl & kMatch) ? kOpEq : kOpX; --i; --j; }
+    else if (fl & kUp) { now = kOpD; --i; }
+    else if (j > 0) { now = kOpI; --j; }
+    else { bad = true; break; }
+    if (now != op) { flush(); op = now; len = 0; }
+    ++len;
+    ++cnt[now];
+  }
+  flush();
+  if (bad) {
+    o[0] = MPC_ALIGN_BAD_SCAN;
+    return;
+  }
+  o[1] = (int32_t)j;
+  for (int k = 0; k < 4; ++k) o[2 + k] = cnt[k];
+  o[6] = n_runs;
+}
+
+void put_int(std::string& s, int64_t v) { s += std::to_string(v); }
+
+// One read's PAF line (empty: no '=' op).
+void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool minus, const int32_t* o, const int32_t* runs,
+                const char* name, size_t name_len, const char* tname, std::string& line) {
+  const int64_t m = job[1], n = job[3], end = job[5];
+  const int32_t n_runs = o[6];
+  // runs are end -> start: the kept span is [first, last] in that order between the outermost '=' runs
+  int32_t first = 0, last = n_runs - 1;
+  int64_t b_q = 0, b_t = 0, a_q = 0, a_t = 0;  // dropped read / target bases: trailing (b), leading (a)
+  while (first < n_runs && (runs[first] & 3) != kOpEq) {
+    const int64_t len = runs[first] >> 2, op = runs[first] & 3;
+    if (op != kOpI) b_q += len;
+    if (op != kOpD) b_t += len;
+    ++first;
+  }
+  if (first == n_runs) return;
+  while ((runs[last] & 3) != kOpEq) {
+    const int64_t len = runs[last] >> 2, op = runs[last] & 3;
+    if (op != kOpI) a_q += len;
+    if (op != kOpD) a_t += len;
+    --last;
+  }
+  const int64_t ts = o[1] + a_t, te = end - b_t;
+  int64_t n_eq = 0, n_ops = 0;
+  for (int32_t k = first; k <= last; ++k) {
+    n_ops += runs[k] >> 2;
+    if ((runs[k] & 3) == kOpEq) n_eq += runs[k] >> 2;
+  }
+  line.append(name, name_len);
+  line += '\t'; put_int(line, m);
+  line += '\t'; put_int(line, minus ? b_q : a_q);
+  line += '\t'; put_int(line, minus ? m - a_q : m - b_q);
+  line += '\t'; line += minus ? '-' : '+';
+  line += '\t'; line += tname;
+  line += '\t'; put_int(line, n);
+  line += '\t'; put_int(line, ts);
+  line += '\t'; put_int(line, te);
+  line += '\t'; put_int(line, n_eq);
+  line += '\t'; put_int(line, n_ops);
+  line += "\t255\tNM:i:"; put_int(line, n_ops - n_eq);
+  line += "\tcs:Z:";
+  int64_t i = a_q, j = ts;
+  for (int32_t k = last; k >= first; --k) {
+    const int64_t len = runs[k] >> 2;
+    switch (runs[k] & 3) {
+      case kOpEq:
+        line += ':'; put_int(line, len);
+        i += len; j += len;
+        break;
+      case kOpX:
+        for (int64_t x = 0; x < len; ++x) { line += '*'; line += lower(t[j + x]); line += lower(q[i + x]); }
+        i += len; j += len;
+        break;
+      case kOpD:  // a read base missing from the target: an insertion
+        line += '+';
+        for (int64_t x = 0; x < len; ++x) line += lower(q[i + x]);
+        i += len;
+        break;
+      default:  // an extra target base: a deletion
+        line += '-';
+        for (int64_t x = 0; x < len; ++x) line += lower(t[j + x]);
+        j += len;
+    }
+  }
+  line += '\n';
+}
+
+}  // namespace
+
+extern "C" const char* mpc_align_last_error(void) { return g_aerr.c_str(); }
+
+extern "C" int mpc_align_revcomp_host(uint8_t* seq, int64_t seq_bytes, const int64_t* tab, int32_t n_reads, int threads) {
+  if (n_reads < 0) return afail("mpc_align_revcomp_host: n_reads < 0");
+  if (n_reads == 0) return kOk;
+  if (!seq || !tab) return afail("mpc_align_revcomp_host: null pointer");
+  for (int32_t r = 0; r < n_reads; ++r) {
+    const int64_t src = tab[3 * (int64_t)r], len = tab[3 * (int64_t)r + 1], dst = tab[3 * (int64_t)r + 2];
+    if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len ||
+        (len > 0 && src < dst + len && dst < src + len))
+      return afail("mpc_align_revcomp_host: read " + std::to_string(r) + ": span outside the blob or overlapping");
+  }
+  const int nt = clamp_threads(threads, n_reads);
+  std::atomic<int32_t> next{0};
+  mpc_host::parallel(nt, [&](int) {
+    for (int32_t r; (r = next.fetch_add(64)) < n_reads;)
+      for (int32_t k = r; k < std::min(n_reads, r + 64); ++k) {
+        const int64_t src = tab[3 * (int64_t)k], len = tab[3 * (int64_t)k + 1], dst = tab[3 * (int64_t)k + 2];
+        for (int64_t x = 0; x < len; ++x) seq[dst + x] = complement(seq[src + len - 1 - x]);
+      }
+  });
+  return kOk;
+}
+
+extern "C" int mpc_align_plan(const int32_t* scan, const int32_t* lens, int32_t n_reads, double max_error,
+                              int64_t workspace_bytes, int64_t* plan, int32_t* cuts, int32_t* n_launches) {
+  if (n_reads < 0) return afail("mpc_align_plan: n_reads < 0");
+  if (!n_launches || !cuts || (n_reads > 0 && (!scan || !lens || !plan))) return afail("mpc_align_plan: null pointer");
+  if (!(max_error >= 0.0) || workspace_bytes < 0) return afail("mpc_align_plan: max_error or workspace_bytes < 0");
+  int32_t nl = 0;
+  int64_t flag_off = 0, run_off = 0;
+  bool open = false;  // the current launch holds a mapped read
+  cuts[0] = 0;
+  for (int32_t r = 0; r < n_reads; ++r) {
+    const int32_t* s = scan + 4 * (int64_t)r;
+    int64_t* p = plan + 8 * (int64_t)r;
+    const int64_t m = lens[r];
+    if (m < 1 || m > MPC_VERIFY_MAX_QUERY) return afail("mpc_align_plan: read " + std::to_string(r) + ": length outside [1, 65536]");
+    if (s[0] < 0 || s[2] < 0 || s[1] < 0 || s[3] < 0) return afail("mpc_align_plan: read " + std::to_string(r) + ": negative scan result");
+    const bool minus = s[2] < s[0];  // a tie is '+'
+    const int64_t d = minus ? s[2] : s[0], end = minus ? s[3] : s[1];
+    const double lim = std::floor(max_error * (double)m);
+    const bool mapped = (double)d <= lim && d <= MPC_ALIGN_MAX_EDITS;
+    p[0] = minus; p[1] = mapped; p[2] = d; p[3] = end; p[4] = 2 * d + 1;
+    p[5] = p[6] = p[7] = 0;
+    if (!mapped) continue;
+    const int64_t need = m * row_pitch(d);
+    if (need > workspace_bytes)
+      return afail("mpc_align_plan: read " + std::to_string(r) + " needs " + std::to_string(need) +
+                   " flag bytes, the workspace budget is " + std::to_string(workspace_bytes));
+    if (open && flag_off + need > workspace_bytes) {  // close the launch before this read
+      cuts[++nl] = r;
+      flag_off = run_off = 0;
+      open = false;
+    }
+    p[5] = need; p[6] = flag_off; p[7] = run_off;
+    flag_off += need;
+    run_off += 2 * d + 1;
+    open = true;
+  }
+  cuts[++nl] = n_reads;
+  if (n_reads == 0) nl = 0;
+  *n_launches = nl;
+  return kOk;
+}
+
+extern "C" int mpc_align_trace_host(const uint8_t* seq, int64_t seq_bytes, const int64_t* jobs, int32_t n_jobs,
+                                    int32_t* out, int32_t* runs, int64_t runs_cap, int threads) {
+  if (n_jobs < 0) return afail("mpc_align_trace_host: n_jobs < 0");
+  if (n_jobs == 0) return kOk;
+  if (!seq || !jobs || !out || !runs) return afail("mpc_align_trace_host: null pointer");
+  for (int32_t r = 0; r < n_jobs; ++r)
+    if (const char* bad = check_job(jobs + 8 * (int64_t)r, seq_bytes, runs_cap))
+      return afail("mpc_align_trace_host: read " + std::to_string(r) + ": " + bad);
+  const int nt = clamp_threads(threads, n_jobs);
+  std::atomic<int32_t> next{0};
+  std::atomic<int> oom{0};
+  mpc_host::parallel(nt, [&](int) {
+    Band s;
+    for (int32_t r; (r = next.fetch_add(1)) < n_jobs;) {
+      const int64_t* j = jobs + 8 * (int64_t)r;
+      try {
+        trace_one(seq + j[0], seq + j[2], j, out + 8 * (int64_t)r, runs + j[7], s);
+      } catch (const std::bad_alloc&) {
+        oom = 1;
+        return;
+      }
+    }
+  });
+  if (oom) return afail("mpc_align_trace_host: out of memory for a band");
+  for (int32_t r = 0; r < n_jobs; ++r)
+    if (out[8 * (int64_t)r] != MPC_ALIGN_OK)
+      return afail("mpc_align_trace_host: read " + std::to_string(r) + ": the band does not give the scan's distance at (m, end)",
+                   MPC_ALIGN_E_SCAN);
+  return kOk;
+}
+
+extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int64_t* jobs, int32_t n_jobs,
+                                const uint8_t* strand, const int32_t* out, const int32_t* runs, int64_t runs_cap,
+                                const char* names, const int64_t* name_off, const char* tname, char* buf, int64_t buf_cap,
+                                int64_t* line_len, int64_t* written, int threads) {
+  if (n_jobs < 0) return afail("mpc_align_render: n_jobs < 0");
+  if (!written) return afail("mpc_align_render: null pointer");
+  *written = 0;
+  if (n_jobs == 0) return kOk;
+  if (!seq || !jobs || !strand || !out || !runs || !names || !name_off || !tname || !line_len || (!buf && buf_cap > 0))
+    return afail("mpc_align_render: null pointer");
+  for (int32_t r = 0; r < n_jobs; ++r) {
+    const int64_t* j = jobs + 8 * (int64_t)r;
+    const int32_t* o = out + 8 * (int64_t)r;
+    const char* bad = check_job(j, seq_bytes, runs_cap);
+    if (!bad && o[0] != MPC_ALIGN_OK) bad = "status is not MPC_ALIGN_OK";
+    if (!bad && (o[6] < 0 || o[6] > 2 * j[4] + 1 || o[1] < 0 || o[1] > j[5])) bad = "trace output outside its bounds";
+    if (!bad && name_off[r + 1] < name_off[r]) bad = "name offsets descend";
+    if (bad) return afail("mpc_align_render: read " + std::to_string(r) + ": " + bad);
+    // the runs must walk exactly the read and the target span (they index both sequences)
+    int64_t qn = 0, tn = 0;
+    for (int32_t k = 0; k < o[6]; ++k) {
+      const int64_t len = runs[j[7] + k] >> 2, op = runs[j[7] + k] & 3;
+      if (len < 1) { qn = -1; break; }
+      if (op != kOpI) qn += len;
+      if (op != kOpD) tn += len;
+    }
+    if (qn != j[1] || tn != j[5] - o[1]) return afail("mpc_align_render: read " + std::to_string(r) + ": runs do not span the read");
+  }
+  // contiguous shares of reads per thread, joined in order
+  const int nt = clamp_threads(threads, n_jobs);
+  std::vector<std::string> part((size_t)nt);
+  mpc_host::parallel(nt, [&](int k) {
+    const int32_t r0 = (int32_t)((int64_t)n_jobs * k / nt), r1 = (int32_t)((int64_t)n_jobs * (k + 1) / nt);
+    std::string& s = part[(size_t)k];
+    for (int32_t r = r0; r < r1; ++r) {
+      const int64_t* j = jobs + 8 * (int64_t)r;
+      const size_t before = s.size();
+      render_one(seq + j[0], seq + j[2], j, strand[r] != 0, out + 8 * (int64_t)r, runs + j[7], names + name_off[r],
+                 (size_t)(name_off[r + 1] - name_off[r]), tname, s);
+      line_len[r] = (int64_t)(s.size() - before);
+    }
+  });
+  int64_t total = 0;
+  for (const std::string& s : part) total += (int64_t)s.size();
+  *written = total;
+  if (total > buf_cap) return afail("mpc_align_render: the buffer holds " + std::to_string(buf_cap) + " bytes, the lines need " + std::to_string(total));
+  int64_t at = 0;
+  for (const std::string& s : part) {
+    std::memcpy(buf + at, s.data(), s.size());
+    at += (int64_t)s.size();
+  }
+  return kOk;
+}

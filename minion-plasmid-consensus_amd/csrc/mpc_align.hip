@@ -1,0 +1,296 @@
+// mpc_align.hip -- the device half of align_reads on gfx950 (include/mpc_align.h;
+// DESIGN.md "align_reads").
+//
+//   K_arevcomp  the reverse complements of a batch's reads, one workgroup per read
+//   K_atrace    band DP + canonical traceback + run encoding, one wave64 per read:
+//               the device form of mpc_verify_script for many reads at once
+//
+// K_atrace keeps ONE row of band values in LDS (W + 1 ints, updated in place:
+// row i - 1's column j - 1 is slot b, its column j is slot b + 1).  The lanes
+// sit across 64 consecutive slots of the row; the left-move chain
+// D[i][b] = min_k<=b x[k] + (b - k) is a DPP prefix maximum of BIAS - (x[k] - k)
+// plus one carried value per 64 slots.  Each cell leaves one flag byte (which
+// moves reproduce its value) in the read's workspace rows, 64 coalesced bytes
+// per store.  The traceback reads those flags back in tiles of 64 rows x 64
+// slots staged through LDS (64 independent loads, one wait), not one dependent
+// global load per step.  Every index follows from the job's own m, n, d, end,
+// which the kernel checks again: a wrong d gives a status, never an access
+// outside the read's rows.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "mpc.h"
+#include "mpc_align.h"
+#include "mpc_device.h"
+
+// mpc_plan.cpp: sets the message mpc_last_error() returns
+__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
+
+namespace {
+using namespace mpc;
+
+constexpr int kInf = 1 << 20;   // above every reachable value (<= 65,536 + 8,193)
+constexpr int kBias = 1 << 21;  // keeps BIAS - (x - lane) positive for the max-scan
+constexpr int kTile = 64;       // traceback tile: 64 rows x 64 slots
+constexpr uint32_t kDiag = 1, kUp = 2, kMatch = 4;
+
+__device__ __forceinline__ uint32_t vcode(uint32_t c, uint32_t other) {
+  switch (c) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+  }
+  return other;
+}
+
+__device__ __forceinline__ uint32_t complement(uint32_t c) {
+  switch (c) {
+    case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
+    case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
+  }
+  return c;
+}
+
+__host__ __device__ inline int64_t row_pitch(int64_t d) { return (2 * d + 1 + 63) / 64 * 64; }
+
+// grid: one 256-thread workgroup per read
+__global__ __launch_bounds__(256) void K_arevcomp(uint8_t* __restrict__ seq, const int64_t seq_bytes,
+                                                  const int64_t* __restrict__ tab) {
+  const int64_t r = blockIdx.x;
+  const int64_t src = tab[3 * r], len = tab[3 * r + 1], dst = tab[3 * r + 2];
+  if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len) return;  // (the host refuses these)
+  for (int64_t x = threadIdx.x; x < len; x += 256) seq[dst + x] = (uint8_t)complement(seq[src + len - 1 - x]);
+}
+
+// One wave per workgroup: its LDS accesses execute in program order, so lanes
+// that read what other lanes wrote need no barrier, only that the compiler
+// keeps the order -- and no wait for the flag stores still in flight, which a
+// __syncthreads() would add to every 64 cells.
+__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// grid: one 64-thread workgroup per read; dynamic LDS: the flag tile, row_cap ints, row_cap + 64 target codes
+__global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, const int64_t seq_bytes,
+                                               const int64_t* __restrict__ jobs, uint8_t* __restrict__ flags,
+                                               const int64_t flags_bytes, int32_t* __restrict__ out,
+                                               int32_t* __restrict__ runs, const int64_t runs_cap, const int32_t row_cap) {
+  extern __shared__ int32_t lds[];
+  uint8_t* tile = (uint8_t*)lds;            // kTile x 64 bytes
+  int32_t* row = lds + kTile * 64 / 4;      // W + 1 ints
+  uint8_t* tw = (uint8_t*)(row + row_cap);  // W + 63 target codes
+  const int ln = lane();
+  const int64_t r = blockIdx.x;
+  const int64_t* jb = jobs + 8 * r;
+  const int64_t q_off = jb[0], m64 = jb[1], t_off = jb[2], n64 = jb[3], d64 = jb[4], end64 = jb[5], flag_off = jb[6],
+                run_off = jb[7];
+  int32_t* o = out + 8 * r;
+  bool ok = m64 >= 1 && m64 <= MPC_VERIFY_MAX_QUERY && n64 >= 1 && n64 <= INT32_MAX && d64 >= 0 &&
+            d64 <= MPC_ALIGN_MAX_EDITS && end64 >= 0 && end64 <= n64;
+  ok = ok && q_off >= 0 && q_off <= seq_bytes - m64 && t_off >= 0 && t_off <= seq_bytes - n64;
+  ok = ok && 2 * d64 + 2 <= row_cap && run_off >= 0 && run_off <= runs_cap - (2 * d64 + 1);
+  ok = ok && flag_off >= 0 && flag_off <= flags_bytes - m64 * row_pitch(d64);
+  if (!ok) {  // (the host refuses these)
+    if (ln < 8) o[ln] = ln == 0 ? MPC_ALIGN_BAD_JOB : 0;
+    return;
+  }
+  const int m = (int)m64, n = (int)n64, d = (int)d64, end = (int)end64;
+  const int W = 2 * d + 1, P = (int)row_pitch(d), d0 = end - m;
+  const uint8_t* q = seq + q_off;
+  const uint8_t* t = seq + t_off;
+  uint8_t* F = flags + flag_off;  // row i at (i - 1) * P
+  int32_t* rn = runs + run_off;
+
+  for (int b = ln; b <= W; b += 64) {
+    const int j = d0 - d + b;
+    row[b] = (b < W && j >= 0 && j <= n) ? 0 : kInf;  // D[0][j] = 0; slot W stays infinite
+  }
+
+  for (int i0 = 1; i0 <= m; i0 += 64) {
+    // 64 rows at a time: their query codes in one register, the W + 63 target codes they meet in LDS
+    lds_fence();  // the previous rows no longer read tw
+    const int tb = i0 + d0 - d - 1;  // target index of row i0's slot 0
+    for (int x = ln; x < W + 63; x += 64) {
+      const int jj = tb + x;
+      tw[x] = (jj >= 0 && jj < n) ? (uint8_t)vcode(t[jj], 5) : (uint8_t)5;
+    }
+    const int qr = i0 - 1 + ln;
+    const uint32_t qv = qr < m ? vcode(q[qr], 4) : 4;
+    lds_fence();
+    const int i1 = min(m, i0 + 63);
+    for (int i = i0; i <= i1; ++i) {
+      const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)qv, i - i0);
+      const int jbase = i + d0 - d;
+      uint8_t* f = F + (int64_t)(i - 1) * P;
+      int carry = kInf;  // D[i][.] at the slot left of this chunk
+      for (int c0 = 0; c0 < W; c0 += 64) {
+        const int b = c0 + ln, j = jbase + b;
+        const bool in = b < W && j >= 0 && j <= n;
+        int x = kInf, dg = kInf, up = kInf;
+        bool eq = false;
+        if (in) {
+          up = row[b + 1] + 1;
+          if (j == 0) {
+            x = i;  // D[i][0] = i
+          } else {
+            eq = qi == tw[i - i0 + b];
+            dg = row[b] + (eq ? 0 : 1);
+            x = min(dg, up);
+          }
+        }
+        // left moves inside the chunk, then the one entering it
+        const int pm = wave_scan_max_i32(kBias - (x - ln));
+        int v = min(ln + kBias - pm, carry + 1 + ln);
+        uint32_t fl = 0;
+        if (in) {
+          if (j == 0) fl = kUp;
+          else fl = (dg == v ? kDiag : 0u) | (up == v ? kUp : 0u) | (eq ? kMatch : 0u);
+        }
+        v = in ? min(v, kInf) : kInf;
+        carry = __builtin_amdgcn_readlane(v, 63);
+        lds_fence();  // every lane has read row[b], row[b + 1]
+        if (b < W) row[b] = v;
+        f[b] = (uint8_t)fl;  // b < P: the pad holds 0; not waited for
+        lds_fence();
+      }
+    }
+  }
+  __syncthreads();  // the flag stores are done before the tiles read them back
+
+  if (uniform_i32(row[d]) != d) {  // (m, end) sits on diagonal d0: slot d
+    if (ln < 8) o[ln] = ln == 0 ? MPC_ALIGN_BAD_SCAN : 0;
+    return;
+  }
+
+  int i = m, j = end, op = -1, len = 0, n_runs = 0;
+  int c_eq = 0, c_x = 0, c_i = 0, c_d = 0;
+  bool bad = false;
+  while (i > 0 && !bad) {
+    const int b = j - i - d0 + d;
+    if (b < 0 || b >= W) { bad = true; break; }
+    const int ws = min(max(b - 32, 0), P - 64), i0 = i;
+    __syncthreads();  // the previous tile is no longer read
+#pragma unroll 8
+    for (int k = 0; k < kTile; ++k) {
+      const int rr = i0 - k;
+      if (rr >= 1) tile[k * 64 + ln] = F[(int64_t)(rr - 1) * P + ws + ln];
+    }
+    __syncthreads();
+    while (i > 0 && i > i0 - kTile) {
+      const int bb = j - i - d0 + d - ws;
+      if (bb < 0 || bb >= 64 || bb + ws >= W) break;  // next tile (or, outside the band, the check above)
+      const uint32_t fl = (uint32_t)uniform_i32(tile[(i0 - i) * 64 + bb]);  // (every lane walks the same path)
+      int now;
+      if (j > 0 && (fl & kDiag)) {
+        now = (fl & kMatch) ? 0 : 1;
+        --i; --j;
+      } else if (fl & kUp) {
+        now = 3;
+        --i;
+      } else if (j > 0) {
+        now = 2;
+        --j;
+      } else {
+        bad = true;
+        break;
+      }
+      if (now != op) {
+        if (len > 0) {
+          if (n_runs < W) { if (ln == 0) rn[n_runs] = (len << 2) | op; }
+          else bad = true;
+          ++n_runs;
+        }
+        op = now;
+        len = 0;
+      }
+      ++len;
+      c_eq += now == 0; c_x += now == 1; c_i += now == 2; c_d += now == 3;
+    }
+  }
+  if (len > 0) {
+    if (n_runs < W) { if (ln == 0) rn[n_runs] = (len << 2) | op; }
+    else bad = true;
+    ++n_runs;
+  }
+  if (bad) {
+    if (ln < 8) o[ln] = ln == 0 ? MPC_ALIGN_BAD_SCAN : 0;
+    return;
+  }
+  if (ln == 0) {
+    o[0] = MPC_ALIGN_OK; o[1] = j; o[2] = c_eq; o[3] = c_x; o[4] = c_i; o[5] = c_d; o[6] = n_runs; o[7] = 0;
+  }
+}
+
+int hip_fail(const char* what, hipError_t e) {
+  return mpc_fail_(MPC_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
+}
+
+}  // namespace
+
+extern "C" int mpc_align_revcomp(uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_tab, int32_t n_reads, void* stream) {
+  if (n_reads < 0) return mpc_fail_(MPC_E_ARG, "mpc_align_revcomp: n_reads < 0");
+  if (n_reads == 0) return MPC_OK;
+  if (!d_seq || !d_tab || seq_bytes < 0) return mpc_fail_(MPC_E_ARG, "mpc_align_revcomp: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> h((size_t)n_reads * 3);
+  hipError_t e = hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail("mpc_align_revcomp: read table", e);
+  for (int32_t r = 0; r < n_reads; ++r) {
+    const int64_t src = h[(size_t)r * 3], len = h[(size_t)r * 3 + 1], dst = h[(size_t)r * 3 + 2];
+    if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len ||
+        (len > 0 && src < dst + len && dst < src + len))
+      return mpc_fail_(MPC_E_ARG, ("mpc_align_revcomp: read " + std::to_string(r) + ": span outside the blob or overlapping").c_str());
+  }
+  hipLaunchKernelGGL(K_arevcomp, dim3((unsigned)n_reads), dim3(256), 0, st, d_seq, seq_bytes, d_tab);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("K_arevcomp", e);
+  return MPC_OK;
+}
+
+extern "C" int mpc_align_trace(const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_jobs, int32_t n_jobs,
+                               uint8_t* d_flags, int64_t flags_bytes, int32_t* d_out, int32_t* d_runs, int64_t runs_cap,
+                               void* stream) {
+  if (n_jobs < 0) return mpc_fail_(MPC_E_ARG, "mpc_align_trace: n_jobs < 0");
+  if (n_jobs == 0) return MPC_OK;
+  if (!d_seq || !d_jobs || !d_flags || !d_out || !d_runs || seq_bytes < 0 || flags_bytes < 0 || runs_cap < 0)
+    return mpc_fail_(MPC_E_ARG, "mpc_align_trace: null pointer or negative size");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> h((size_t)n_jobs * 8);
+  hipError_t e = hipMemcpyAsync(h.data(), d_jobs, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail("mpc_align_trace: job table", e);
+  int64_t flag_next = 0, d_max = 0;
+  for (int32_t r = 0; r < n_jobs; ++r) {
+    const int64_t* j = &h[(size_t)r * 8];
+    const int64_t q_off = j[0], m = j[1], t_off = j[2], n = j[3], d = j[4], end = j[5], flag_off = j[6], run_off = j[7];
+    const char* bad = nullptr;
+    if (m < 1 || m > MPC_VERIFY_MAX_QUERY) bad = "read length outside [1, MPC_VERIFY_MAX_QUERY]";
+    else if (n < 1 || n > INT32_MAX) bad = "target length outside [1, 2^31)";
+    else if (d < 0 || d > MPC_ALIGN_MAX_EDITS) bad = "distance outside [0, MPC_ALIGN_MAX_EDITS]";
+    else if (end < 0 || end > n) bad = "end outside [0, n]";
+    else if (q_off < 0 || q_off > seq_bytes - m || t_off < 0 || t_off > seq_bytes - n) bad = "sequence outside the blob";
+    else if (run_off < 0 || run_off > runs_cap - (2 * d + 1)) bad = "runs outside the run buffer";
+    else if (flag_off < flag_next || flag_off > flags_bytes - m * row_pitch(d)) bad = "flag rows outside the workspace or not ascending";
+    if (bad) return mpc_fail_(MPC_E_ARG, ("mpc_align_trace: read " + std::to_string(r) + ": " + bad).c_str());
+    flag_next = flag_off + m * row_pitch(d);
+    d_max = d > d_max ? d : d_max;
+  }
+  const int32_t row_cap = (int32_t)((2 * d_max + 2 + 63) / 64 * 64);
+  const size_t lds_bytes = (size_t)kTile * 64 + (size_t)row_cap * sizeof(int32_t) + (size_t)row_cap + 64;
+  hipLaunchKernelGGL(K_atrace, dim3((unsigned)n_jobs), dim3(64), lds_bytes, st, d_seq, seq_bytes, d_jobs, d_flags,
+                     flags_bytes, d_out, d_runs, runs_cap, row_cap);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("K_atrace", e);
+  std::vector<int32_t> ho((size_t)n_jobs * 8);
+  e = hipMemcpyAsync(ho.data(), d_out, ho.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail("K_atrace", e);
+  for (int32_t r = 0; r < n_jobs; ++r)
+    if (ho[(size_t)r * 8] != MPC_ALIGN_OK)
+      return mpc_fail_(MPC_ALIGN_E_SCAN, ("mpc_align_trace: read " + std::to_string(r) + ": status " +
+                                          std::to_string(ho[(size_t)r * 8]) + ": the band does not give the scan's distance at (m, end)").c_str());
+  return MPC_OK;
+}
