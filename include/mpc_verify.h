@@ -55,8 +55,8 @@ int mpc_verify_scan_host(const uint8_t* seq, const int64_t* pairs, int32_t n_pai
 
 /* The canonical edit script of one pair, given the scan's (distance, end):
  * a DP over the band of diagonals |(j - i) - (end - m)| <= distance, which
- * holds every optimal path (memory m x (2 distance + 1) bytes), then the
- * traceback above.  counts = number of '=', 'X', 'I', 'D' ops; cigar = their
+ * holds every optimal path (memory m x roundup(2 distance + 1, 64) bytes),
+ * then the traceback above.  counts = number of '=', 'X', 'I', 'D' ops; cigar = their
  * run-length encoding from start to end (e.g. "1998=1X12=2D640="), NUL
  * terminated.  Fails (MPC_E_ARG) when the band's value at (m, end) is not
  * `distance` -- a cross-check of the scan -- or when cigar_cap is too small.

@@ -23,12 +23,12 @@ LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 
 HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip", "mpc_link.hip", "mpc_align.hip"]
 HOST_SOURCES = ["mpc_plan.cpp"]  # libmpc.so's host planner (g++, no HIP)
-HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h", "mpc_cstables.h",
+HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h", "mpc_cstables.h", "mpc_bandtrace.h",
                # the stages of mpc_kernels.hip (one translation unit), in pipeline order
                "mpc_k_common.h", "mpc_k_parse.h", "mpc_k_index.h", "mpc_k_left.h", "mpc_k_wrap.h", "mpc_k_layout.h",
                "mpc_k_rows.h", "mpc_k_call.h"]
 INGEST_SOURCES = ["ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp", "align.cpp"]
-INGEST_HEADERS = ["host_threads.h", "mpc_cswalk_host.h", "mpc_cstables.h"]  # csrc headers of libmpc_ingest.so
+INGEST_HEADERS = ["host_threads.h", "mpc_cswalk_host.h", "mpc_cstables.h", "mpc_bandtrace.h"]  # csrc headers of libmpc_ingest.so
 
 
 def _stale(target, sources):

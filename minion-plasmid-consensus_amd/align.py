@@ -20,6 +20,9 @@ import ctypes
 
 import numpy as np
 
+from . import verify
+from .verify import _device, _to_device  # (the scan's device plumbing: libmpc.so before torch)
+
 MAX_QUERY = 65536                 # mpc_verify.h MPC_VERIFY_MAX_QUERY
 MAX_EDITS = 4096                  # mpc_align.h MPC_ALIGN_MAX_EDITS
 DEFAULT_WORKSPACE = 2 << 30       # mpc_align.h MPC_ALIGN_DEFAULT_WORKSPACE
@@ -88,7 +91,6 @@ def read_batches(path, batch_bases=DEFAULT_BATCH_BASES):
 
 def host_lib():
     """libmpc_ingest.so with the align entry points bound."""
-    from . import verify
     try:
         L = verify.host_lib()
     except verify.VerifyError as e:
@@ -114,36 +116,16 @@ def _host_error(L):
 
 
 def device_lib():
-    """libmpc.so with the align entry points bound (before torch: one HIP runtime in the process)."""
-    from . import engine
-    L = engine.lib()
+    """libmpc.so with the align entry points bound (the scan's: verify.device_lib)."""
+    L = verify.device_lib()
     if not hasattr(L, "_align_ready"):
         vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        L.mpc_verify_scan.restype = ctypes.c_int
-        L.mpc_verify_scan.argtypes = [vp, vp, i32, vp, vp]
         L.mpc_align_revcomp.restype = ctypes.c_int
         L.mpc_align_revcomp.argtypes = [vp, i64, vp, i32, vp]
         L.mpc_align_trace.restype = ctypes.c_int
         L.mpc_align_trace.argtypes = [vp, i64, vp, i32, vp, i64, vp, vp, i64, vp]
         L._align_ready = True
     return L
-
-
-def _device(device):
-    from . import engine
-    device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        raise engine.MpcError("no HIP device visible (use device='cpu' for the host path)")
-    return torch, torch.device("cuda", int(device))
-
-
-def _to_device(torch, dev, a):
-    a = np.ascontiguousarray(a)
-    d = torch.empty(a.nbytes, dtype=torch.uint8, device=dev)
-    if a.nbytes:
-        d.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8)))
-    return d
 
 
 # ---- the steps, one batch at a time --------------------------------------------
@@ -185,29 +167,26 @@ def orient_and_scan(pk, device=0, threads=0):
     R = len(pk.lens)
     if R == 0:
         return np.zeros((0, 4), np.int32)
-    rc_tab, pairs = pk.revcomp_table(), pk.pair_table()
+    rc_tab = pk.revcomp_table()
     if device == "cpu":
         L = host_lib()
         if L.mpc_align_revcomp_host(pk.seq.ctypes.data, pk.seq.nbytes, rc_tab.ctypes.data, R, threads) != 0:
             raise AlignError(_host_error(L))
-        out = np.zeros((R, 4), np.int32)
-        if L.mpc_verify_scan_host(pk.seq.ctypes.data, pairs.ctypes.data, 2 * R, out.ctypes.data, threads) != 0:
-            raise AlignError(L.mpc_verify_last_error().decode(errors="replace"))
-        return out
-    from . import engine
-    torch, dev = _device(device)
-    L = device_lib()
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        pk.d_seq = _to_device(torch, dev, pk.seq)
-        d_tab, d_pairs = _to_device(torch, dev, rc_tab), _to_device(torch, dev, pairs)
-        d_out = torch.empty(4 * R, dtype=torch.int32, device=dev)
-        engine._check(L.mpc_align_revcomp(pk.d_seq.data_ptr(), pk.seq.nbytes, d_tab.data_ptr(), R, stream))
-        engine._check(L.mpc_verify_scan(pk.d_seq.data_ptr(), d_pairs.data_ptr(), 2 * R, d_out.data_ptr(), stream))
-        out = d_out.cpu().numpy().reshape(R, 4)
-        a, b = pk.minus_span
-        pk.seq[a:b] = pk.d_seq[a:b].cpu().numpy()  # the renderer reads the oriented reads on the host
-    return out
+    else:
+        from . import engine
+        torch, dev = _device(device)
+        L = device_lib()
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            pk.d_seq = _to_device(torch, dev, pk.seq)
+            d_tab = _to_device(torch, dev, rc_tab)
+            engine._check(L.mpc_align_revcomp(pk.d_seq.data_ptr(), pk.seq.nbytes, d_tab.data_ptr(), R, stream))
+            a, b = pk.minus_span
+            pk.seq[a:b] = pk.d_seq[a:b].cpu().numpy()  # the renderer reads the oriented reads on the host
+    try:
+        return verify.scan_table(pk.seq, pk.pair_table(), device, threads, d_seq=pk.d_seq).reshape(R, 4)
+    except verify.VerifyError as e:
+        raise AlignError(str(e))
 
 
 def plan(scan, lens, max_error=0.2, workspace_bytes=DEFAULT_WORKSPACE):

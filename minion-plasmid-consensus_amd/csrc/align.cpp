@@ -1,7 +1,7 @@
 // align.cpp -- host half of align_reads (include/mpc_align.h):
 //   mpc_align_revcomp_host  the minus-strand queries (--device cpu)
 //   mpc_align_plan          strand, mapped or not, band sizes, launch cuts
-//   mpc_align_trace_host    scalar band DP + canonical traceback + run encoding:
+//   mpc_align_trace_host    the band trace of mpc_bandtrace.h over a job table:
 //                           the CPU checker of K_atrace, the timing baseline,
 //                           --device cpu
 //   mpc_align_render        end rule + PAF lines of a batch
@@ -16,8 +16,11 @@
 
 #include "host_threads.h"
 #include "mpc_align.h"
+#include "mpc_bandtrace.h"
 
 namespace {
+using namespace mpc_band;
+using mpc_host::clamp_threads;
 
 constexpr int kOk = 0, kArg = -1;  // MPC_OK, MPC_E_ARG of mpc.h
 
@@ -27,139 +30,7 @@ int afail(const std::string& msg, int code = kArg) {
   return code;
 }
 
-// A C G T -> 0..3 after upper-casing; any other byte -> `other` (mpc_verify.h)
-inline uint8_t vcode(uint8_t c, uint8_t other) {
-  switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-  }
-  return other;
-}
-
-inline uint8_t complement(uint8_t c) {
-  switch (c) {
-    case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
-    case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
-  }
-  return c;
-}
-
 inline char lower(uint8_t c) { return (char)((c >= 'A' && c <= 'Z') ? c + 32 : c); }
-
-inline int64_t row_pitch(int64_t d) { return (2 * d + 1 + 63) / 64 * 64; }
-
-int clamp_threads(int threads, int64_t work) {
-  const int nt = threads > 0 ? threads : mpc_host::host_threads();
-  return (int)std::max<int64_t>(1, std::min<int64_t>(nt, work));
-}
-
-// what the host refuses before any read is traced (K_atrace's launch checks the same)
-const char* check_job(const int64_t* j, int64_t seq_bytes, int64_t runs_cap) {
-  const int64_t q_off = j[0], m = j[1], t_off = j[2], n = j[3], d = j[4], end = j[5], run_off = j[7];
-  if (m < 1 || m > MPC_VERIFY_MAX_QUERY) return "read length outside [1, MPC_VERIFY_MAX_QUERY]";
-  if (n < 1 || n > INT32_MAX) return "target length outside [1, 2^31)";
-  if (d < 0 || d > MPC_ALIGN_MAX_EDITS) return "distance outside [0, MPC_ALIGN_MAX_EDITS]";
-  if (end < 0 || end > n) return "end outside [0, n]";
-  if (q_off < 0 || q_off > seq_bytes - m || t_off < 0 || t_off > seq_bytes - n) return "sequence outside the blob";
-  if (run_off < 0 || run_off > runs_cap - (2 * d + 1)) return "runs outside the run buffer";
-  return nullptr;
-}
-
-enum : uint8_t { kDiag = 1, kUp = 2, kMatch = 4 };
-enum : int32_t { kOpEq = 0, kOpX = 1, kOpI = 2, kOpD = 3 };
-
-struct Band {  // one thread's scratch, grown as needed
-  std::vector<uint8_t> flags, tc;
-  std::vector<int32_t> row;
-};
-
-// One read: the definition's band DP (row i over slots b, one row of values kept
-// in place), the traceback from (m, end) and the runs, end -> start.
-void trace_one(const uint8_t* q, const uint8_t* t, const int64_t* job, int32_t* o, int32_t* runs, Band& s) {
-  const int64_t m = job[1], n = job[3], d = job[4], end = job[5];
-  const int64_t W = 2 * d + 1, P = row_pitch(d), d0 = end - m;
-  const int32_t INF = 1 << 20;
-  for (int k = 0; k < 8; ++k) o[k] = 0;
-  s.flags.resize((size_t)(m * P));
-  s.row.resize((size_t)W + 1);
-  // the target bytes any band cell can touch: columns [jlo, jhi]
-  const int64_t jlo = std::max<int64_t>(1, 1 + d0 - d), jhi = std::min<int64_t>(n, end + d);
-  s.tc.resize((size_t)std::max<int64_t>(0, jhi - jlo + 1));
-  for (int64_t j = jlo; j <= jhi; ++j) s.tc[(size_t)(j - jlo)] = vcode(t[j - 1], 5);
-  int32_t* row = s.row.data();
-  for (int64_t b = 0; b < W; ++b) {
-    const int64_t j = d0 - d + b;
-    row[b] = (j >= 0 && j <= n) ? 0 : INF;  // D[0][j] = 0
-  }
-  row[W] = INF;
-  for (int64_t i = 1; i <= m; ++i) {
-    const uint8_t qi = vcode(q[i - 1], 4);
-    uint8_t* f = &s.flags[(size_t)((i - 1) * P)];
-    int32_t left = INF;  // D[i][j - 1]
-    for (int64_t b = 0; b < W; ++b) {
-      const int64_t j = i + d0 - d + b;
-      int32_t v = INF;
-      uint8_t fl = 0;
-      if (j >= 0 && j <= n) {
-        // row i - 1: column j - 1 is slot b, column j is slot b + 1
-        const int32_t up = row[b + 1] + 1;
-        if (j == 0) {
-          v = (int32_t)i;
-          fl = kUp;
-        } else {
-          const bool eq = qi == s.tc[(size_t)(j - jlo)];
-          const int32_t dg = row[b] + (eq ? 0 : 1);
-          v = std::min(dg, std::min(up, left + 1));
-          if (dg == v) fl |= kDiag;
-          if (up == v) fl |= kUp;
-          if (eq) fl |= kMatch;
-        }
-        if (v > INF) v = INF;
-      }
-      row[b] = v;
-      left = v;
-      f[b] = fl;
-    }
-  }
-  if (row[d] != (int32_t)d) {  // (m, end) sits on diagonal d0: slot d
-    o[0] = MPC_ALIGN_BAD_SCAN;
-    return;
-  }
-  int64_t i = m, j = end;
-  int32_t cnt[4] = {0, 0, 0, 0}, n_runs = 0, op = -1, len = 0;
-  const int32_t cap = (int32_t)W;
-  bool bad = false;
-  auto flush = [&]() {
-    if (len > 0) {
-      if (n_runs < cap) runs[n_runs] = (len << 2) | op;
-      else bad = true;
-      ++n_runs;
-    }
-  };
-  while (i > 0) {
-    const int64_t b = j - i - d0 + d;
-    if (b < 0 || b >= W) { bad = true; break; }
-    const uint8_t fl = s.flags[(size_t)((i - 1) * P + b)];
-    int32_t now;
-    if (j > 0 && (fl & kDiag)) { now = (fl & kMatch) ? kOpEq : kOpX; --i; --j; }
-    else if (fl & kUp) { now = kOpD; --i; }
-    else if (j > 0) { now = kOpI; --j; }
-    else { bad = true; break; }
-    if (now != op) { flush(); op = now; len = 0; }
-    ++len;
-    ++cnt[now];
-  }
-  flush();
-  if (bad) {
-    o[0] = MPC_ALIGN_BAD_SCAN;
-    return;
-  }
-  o[1] = (int32_t)j;
-  for (int k = 0; k < 4; ++k) o[2 + k] = cnt[k];
-  o[6] = n_runs;
-}
 
 void put_int(std::string& s, int64_t v) { s += std::to_string(v); }
 
@@ -171,15 +42,15 @@ void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool min
   // runs are end -> start: the kept span is [first, last] in that order between the outermost '=' runs
   int32_t first = 0, last = n_runs - 1;
   int64_t b_q = 0, b_t = 0, a_q = 0, a_t = 0;  // dropped read / target bases: trailing (b), leading (a)
-  while (first < n_runs && (runs[first] & 3) != kOpEq) {
-    const int64_t len = runs[first] >> 2, op = runs[first] & 3;
+  while (first < n_runs && run_op(runs[first]) != kOpEq) {
+    const int64_t len = run_len(runs[first]), op = run_op(runs[first]);
     if (op != kOpI) b_q += len;
     if (op != kOpD) b_t += len;
     ++first;
   }
   if (first == n_runs) return;
-  while ((runs[last] & 3) != kOpEq) {
-    const int64_t len = runs[last] >> 2, op = runs[last] & 3;
+  while (run_op(runs[last]) != kOpEq) {
+    const int64_t len = run_len(runs[last]), op = run_op(runs[last]);
     if (op != kOpI) a_q += len;
     if (op != kOpD) a_t += len;
     --last;
@@ -187,8 +58,8 @@ void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool min
   const int64_t ts = o[1] + a_t, te = end - b_t;
   int64_t n_eq = 0, n_ops = 0;
   for (int32_t k = first; k <= last; ++k) {
-    n_ops += runs[k] >> 2;
-    if ((runs[k] & 3) == kOpEq) n_eq += runs[k] >> 2;
+    n_ops += run_len(runs[k]);
+    if (run_op(runs[k]) == kOpEq) n_eq += run_len(runs[k]);
   }
   line.append(name, name_len);
   line += '\t'; put_int(line, m);
@@ -205,8 +76,8 @@ void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool min
   line += "\tcs:Z:";
   int64_t i = a_q, j = ts;
   for (int32_t k = last; k >= first; --k) {
-    const int64_t len = runs[k] >> 2;
-    switch (runs[k] & 3) {
+    const int64_t len = run_len(runs[k]);
+    switch (run_op(runs[k])) {
       case kOpEq:
         line += ':'; put_int(line, len);
         i += len; j += len;
@@ -237,19 +108,16 @@ extern "C" int mpc_align_revcomp_host(uint8_t* seq, int64_t seq_bytes, const int
   if (n_reads < 0) return afail("mpc_align_revcomp_host: n_reads < 0");
   if (n_reads == 0) return kOk;
   if (!seq || !tab) return afail("mpc_align_revcomp_host: null pointer");
-  for (int32_t r = 0; r < n_reads; ++r) {
-    const int64_t src = tab[3 * (int64_t)r], len = tab[3 * (int64_t)r + 1], dst = tab[3 * (int64_t)r + 2];
-    if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len ||
-        (len > 0 && src < dst + len && dst < src + len))
-      return afail("mpc_align_revcomp_host: read " + std::to_string(r) + ": span outside the blob or overlapping");
-  }
+  for (int32_t r = 0; r < n_reads; ++r)
+    if (const int bad = check_revcomp(tab + 3 * (int64_t)r, seq_bytes))
+      return afail("mpc_align_revcomp_host: read " + std::to_string(r) + ": " + fault_text(bad));
   const int nt = clamp_threads(threads, n_reads);
   std::atomic<int32_t> next{0};
   mpc_host::parallel(nt, [&](int) {
     for (int32_t r; (r = next.fetch_add(64)) < n_reads;)
       for (int32_t k = r; k < std::min(n_reads, r + 64); ++k) {
         const int64_t src = tab[3 * (int64_t)k], len = tab[3 * (int64_t)k + 1], dst = tab[3 * (int64_t)k + 2];
-        for (int64_t x = 0; x < len; ++x) seq[dst + x] = complement(seq[src + len - 1 - x]);
+        for (int64_t x = 0; x < len; ++x) seq[dst + x] = (uint8_t)complement(seq[src + len - 1 - x]);
       }
   });
   return kOk;
@@ -303,8 +171,8 @@ extern "C" int mpc_align_trace_host(const uint8_t* seq, int64_t seq_bytes, const
   if (n_jobs == 0) return kOk;
   if (!seq || !jobs || !out || !runs) return afail("mpc_align_trace_host: null pointer");
   for (int32_t r = 0; r < n_jobs; ++r)
-    if (const char* bad = check_job(jobs + 8 * (int64_t)r, seq_bytes, runs_cap))
-      return afail("mpc_align_trace_host: read " + std::to_string(r) + ": " + bad);
+    if (const int bad = check_job(jobs + 8 * (int64_t)r, seq_bytes, runs_cap))
+      return afail("mpc_align_trace_host: read " + std::to_string(r) + ": " + fault_text(bad));
   const int nt = clamp_threads(threads, n_jobs);
   std::atomic<int32_t> next{0};
   std::atomic<int> oom{0};
@@ -313,7 +181,7 @@ extern "C" int mpc_align_trace_host(const uint8_t* seq, int64_t seq_bytes, const
     for (int32_t r; (r = next.fetch_add(1)) < n_jobs;) {
       const int64_t* j = jobs + 8 * (int64_t)r;
       try {
-        trace_one(seq + j[0], seq + j[2], j, out + 8 * (int64_t)r, runs + j[7], s);
+        band_trace(seq + j[0], j[1], seq + j[2], j[3], j[4], j[5], out + 8 * (int64_t)r, runs + j[7], s);
       } catch (const std::bad_alloc&) {
         oom = 1;
         return;
@@ -341,7 +209,7 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
   for (int32_t r = 0; r < n_jobs; ++r) {
     const int64_t* j = jobs + 8 * (int64_t)r;
     const int32_t* o = out + 8 * (int64_t)r;
-    const char* bad = check_job(j, seq_bytes, runs_cap);
+    const char* bad = fault_text(check_job(j, seq_bytes, runs_cap));
     if (!bad && o[0] != MPC_ALIGN_OK) bad = "status is not MPC_ALIGN_OK";
     if (!bad && (o[6] < 0 || o[6] > 2 * j[4] + 1 || o[1] < 0 || o[1] > j[5])) bad = "trace output outside its bounds";
     if (!bad && name_off[r + 1] < name_off[r]) bad = "name offsets descend";
@@ -349,7 +217,7 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
     // the runs must walk exactly the read and the target span (they index both sequences)
     int64_t qn = 0, tn = 0;
     for (int32_t k = 0; k < o[6]; ++k) {
-      const int64_t len = runs[j[7] + k] >> 2, op = runs[j[7] + k] & 3;
+      const int64_t len = run_len(runs[j[7] + k]), op = run_op(runs[j[7] + k]);
       if (len < 1) { qn = -1; break; }
       if (op != kOpI) qn += len;
       if (op != kOpD) tn += len;

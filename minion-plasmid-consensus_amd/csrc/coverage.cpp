@@ -179,8 +179,7 @@ int mpc_coverage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* t
 
   // every thread walks its cut of the records into rows of its own (thread 0:
   // the output itself); as many threads as fit 1 GiB of such copies
-  int T = threads > 0 ? threads : mpc_host::host_threads();
-  T = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)T, n_records, (int64_t)((1ull << 30) / (n_words * 4 + 1)) + 1}));
+  const int T = mpc_host::clamp_threads(threads, std::min<int64_t>(n_records, (int64_t)((1ull << 30) / (n_words * 4 + 1)) + 1));
   std::vector<std::vector<uint32_t>> priv((size_t)T);
   std::vector<std::vector<uint64_t>> pstat((size_t)T);
   mpc_host::walk_records(n_records, T, status, [&](int k) {
@@ -257,8 +256,7 @@ int mpc_coverage_ingest(const char* paf_path, int mode, int n_threads, mpc_cover
   if (mode != 0 && mode != 1) return ingest_fail(out, "mode is neither 0 (first alignment per read) nor 1 (all)");
   Mapped f;
   if (!f.open(paf_path)) return ingest_fail(out, std::string(paf_path) + ": cannot be read");
-  int T = n_threads > 0 ? n_threads : mpc_host::host_threads();
-  T = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, f.n / (1 << 16) + 1));
+  const int T = mpc_host::clamp_threads(n_threads, (long long)(f.n / (1 << 16) + 1));
 
   // cuts at line starts
   std::vector<size_t> cut((size_t)T + 1, f.n);

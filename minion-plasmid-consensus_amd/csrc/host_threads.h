@@ -23,6 +23,12 @@ inline int host_threads() {
   return hw ? (int)hw : 4;
 }
 
+// the threads asked for (<= 0: host_threads()), at most one per unit of work, at least 1
+inline int clamp_threads(int threads, long long work) {
+  const long long nt = threads > 0 ? threads : host_threads();
+  return (int)(nt < work ? nt : work < 1 ? 1 : work);
+}
+
 // f(0) ... f(T - 1), one thread each (T <= 1: f(0) on the caller's), joined on return
 template <class F>
 void parallel(int T, F f) {

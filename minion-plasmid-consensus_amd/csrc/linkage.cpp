@@ -72,8 +72,7 @@ struct SiteFx {
 void count_pairs(const uint8_t* alleles, int64_t N, int K, uint32_t* pair, int threads) {
   const size_t cells = (size_t)K * K * 64;
   std::fill(pair, pair + cells, 0u);
-  int T = threads > 0 ? threads : mpc_host::host_threads();
-  T = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)T, N / 1024 + 1));
+  const int T = mpc_host::clamp_threads(threads, N / 1024 + 1);
   std::vector<std::vector<uint32_t>> priv((size_t)T);
   parallel(T, [&](int t) {
     uint32_t* my = pair;
@@ -132,8 +131,7 @@ int mpc_linkage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* ts
   status[0] = status[1] = 0;
   if (n_records > 0) std::memset(alleles, 0, (size_t)n_records * (size_t)K);
 
-  int T = threads > 0 ? threads : mpc_host::host_threads();
-  T = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)T, n_records));
+  const int T = mpc_host::clamp_threads(threads, n_records);
   mpc_host::walk_records(n_records, T, status, [&](int) {
     return [=](int64_t r) {
       const int32_t s = rec_sample[r];

@@ -2,8 +2,8 @@
 // DESIGN.md "align_reads").
 //
 //   K_arevcomp  the reverse complements of a batch's reads, one workgroup per read
-//   K_atrace    band DP + canonical traceback + run encoding, one wave64 per read:
-//               the device form of mpc_verify_script for many reads at once
+//   K_atrace    the band trace of mpc_bandtrace.h (which describes the band, its
+//               flag bytes and the traceback), one wave64 per read
 //
 // K_atrace keeps ONE row of band values in LDS (W + 1 ints, updated in place:
 // row i - 1's column j - 1 is slot b, its column j is slot b + 1).  The lanes
@@ -24,6 +24,7 @@
 
 #include "mpc.h"
 #include "mpc_align.h"
+#include "mpc_bandtrace.h"
 #include "mpc_device.h"
 
 // mpc_plan.cpp: sets the message mpc_last_error() returns
@@ -31,38 +32,19 @@ __attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
 
 namespace {
 using namespace mpc;
+using namespace mpc_band;
 
 constexpr int kInf = 1 << 20;   // above every reachable value (<= 65,536 + 8,193)
 constexpr int kBias = 1 << 21;  // keeps BIAS - (x - lane) positive for the max-scan
 constexpr int kTile = 64;       // traceback tile: 64 rows x 64 slots
-constexpr uint32_t kDiag = 1, kUp = 2, kMatch = 4;
-
-__device__ __forceinline__ uint32_t vcode(uint32_t c, uint32_t other) {
-  switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-  }
-  return other;
-}
-
-__device__ __forceinline__ uint32_t complement(uint32_t c) {
-  switch (c) {
-    case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
-    case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
-  }
-  return c;
-}
-
-__host__ __device__ inline int64_t row_pitch(int64_t d) { return (2 * d + 1 + 63) / 64 * 64; }
 
 // grid: one 256-thread workgroup per read
 __global__ __launch_bounds__(256) void K_arevcomp(uint8_t* __restrict__ seq, const int64_t seq_bytes,
                                                   const int64_t* __restrict__ tab) {
   const int64_t r = blockIdx.x;
   const int64_t src = tab[3 * r], len = tab[3 * r + 1], dst = tab[3 * r + 2];
-  if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len) return;  // (the host refuses these)
+  // restates the bounds of check_revcomp (mpc_bandtrace.h), which the host applies before the launch
+  if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len) return;
   for (int64_t x = threadIdx.x; x < len; x += 256) seq[dst + x] = (uint8_t)complement(seq[src + len - 1 - x]);
 }
 
@@ -87,12 +69,14 @@ __global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, 
   const int64_t q_off = jb[0], m64 = jb[1], t_off = jb[2], n64 = jb[3], d64 = jb[4], end64 = jb[5], flag_off = jb[6],
                 run_off = jb[7];
   int32_t* o = out + 8 * r;
+  // restates check_job and check_job_flags (flag_next 0) of mpc_bandtrace.h, which the host applies before
+  // the launch, and adds the row_cap the launch was sized by
   bool ok = m64 >= 1 && m64 <= MPC_VERIFY_MAX_QUERY && n64 >= 1 && n64 <= INT32_MAX && d64 >= 0 &&
             d64 <= MPC_ALIGN_MAX_EDITS && end64 >= 0 && end64 <= n64;
   ok = ok && q_off >= 0 && q_off <= seq_bytes - m64 && t_off >= 0 && t_off <= seq_bytes - n64;
   ok = ok && 2 * d64 + 2 <= row_cap && run_off >= 0 && run_off <= runs_cap - (2 * d64 + 1);
   ok = ok && flag_off >= 0 && flag_off <= flags_bytes - m64 * row_pitch(d64);
-  if (!ok) {  // (the host refuses these)
+  if (!ok) {
     if (ln < 8) o[ln] = ln == 0 ? MPC_ALIGN_BAD_JOB : 0;
     return;
   }
@@ -184,13 +168,13 @@ __global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, 
       const uint32_t fl = (uint32_t)uniform_i32(tile[(i0 - i) * 64 + bb]);  // (every lane walks the same path)
       int now;
       if (j > 0 && (fl & kDiag)) {
-        now = (fl & kMatch) ? 0 : 1;
+        now = (fl & kMatch) ? kOpEq : kOpX;
         --i; --j;
       } else if (fl & kUp) {
-        now = 3;
+        now = kOpD;
         --i;
       } else if (j > 0) {
-        now = 2;
+        now = kOpI;
         --j;
       } else {
         bad = true;
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, 
       }
       if (now != op) {
         if (len > 0) {
-          if (n_runs < W) { if (ln == 0) rn[n_runs] = (len << 2) | op; }
+          if (n_runs < W) { if (ln == 0) rn[n_runs] = pack_run(len, op); }
           else bad = true;
           ++n_runs;
         }
@@ -206,11 +190,11 @@ __global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, 
         len = 0;
       }
       ++len;
-      c_eq += now == 0; c_x += now == 1; c_i += now == 2; c_d += now == 3;
+      c_eq += now == kOpEq; c_x += now == kOpX; c_i += now == kOpI; c_d += now == kOpD;
     }
   }
   if (len > 0) {
-    if (n_runs < W) { if (ln == 0) rn[n_runs] = (len << 2) | op; }
+    if (n_runs < W) { if (ln == 0) rn[n_runs] = pack_run(len, op); }
     else bad = true;
     ++n_runs;
   }
@@ -238,12 +222,9 @@ extern "C" int mpc_align_revcomp(uint8_t* d_seq, int64_t seq_bytes, const int64_
   hipError_t e = hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return hip_fail("mpc_align_revcomp: read table", e);
-  for (int32_t r = 0; r < n_reads; ++r) {
-    const int64_t src = h[(size_t)r * 3], len = h[(size_t)r * 3 + 1], dst = h[(size_t)r * 3 + 2];
-    if (len < 0 || src < 0 || dst < 0 || src > seq_bytes - len || dst > seq_bytes - len ||
-        (len > 0 && src < dst + len && dst < src + len))
-      return mpc_fail_(MPC_E_ARG, ("mpc_align_revcomp: read " + std::to_string(r) + ": span outside the blob or overlapping").c_str());
-  }
+  for (int32_t r = 0; r < n_reads; ++r)
+    if (const int bad = check_revcomp(&h[(size_t)r * 3], seq_bytes))
+      return mpc_fail_(MPC_E_ARG, ("mpc_align_revcomp: read " + std::to_string(r) + ": " + fault_text(bad)).c_str());
   hipLaunchKernelGGL(K_arevcomp, dim3((unsigned)n_reads), dim3(256), 0, st, d_seq, seq_bytes, d_tab);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail("K_arevcomp", e);
@@ -265,18 +246,11 @@ extern "C" int mpc_align_trace(const uint8_t* d_seq, int64_t seq_bytes, const in
   int64_t flag_next = 0, d_max = 0;
   for (int32_t r = 0; r < n_jobs; ++r) {
     const int64_t* j = &h[(size_t)r * 8];
-    const int64_t q_off = j[0], m = j[1], t_off = j[2], n = j[3], d = j[4], end = j[5], flag_off = j[6], run_off = j[7];
-    const char* bad = nullptr;
-    if (m < 1 || m > MPC_VERIFY_MAX_QUERY) bad = "read length outside [1, MPC_VERIFY_MAX_QUERY]";
-    else if (n < 1 || n > INT32_MAX) bad = "target length outside [1, 2^31)";
-    else if (d < 0 || d > MPC_ALIGN_MAX_EDITS) bad = "distance outside [0, MPC_ALIGN_MAX_EDITS]";
-    else if (end < 0 || end > n) bad = "end outside [0, n]";
-    else if (q_off < 0 || q_off > seq_bytes - m || t_off < 0 || t_off > seq_bytes - n) bad = "sequence outside the blob";
-    else if (run_off < 0 || run_off > runs_cap - (2 * d + 1)) bad = "runs outside the run buffer";
-    else if (flag_off < flag_next || flag_off > flags_bytes - m * row_pitch(d)) bad = "flag rows outside the workspace or not ascending";
-    if (bad) return mpc_fail_(MPC_E_ARG, ("mpc_align_trace: read " + std::to_string(r) + ": " + bad).c_str());
-    flag_next = flag_off + m * row_pitch(d);
-    d_max = d > d_max ? d : d_max;
+    int bad = check_job(j, seq_bytes, runs_cap);
+    if (!bad) bad = check_job_flags(j, flags_bytes, flag_next);
+    if (bad) return mpc_fail_(MPC_E_ARG, ("mpc_align_trace: read " + std::to_string(r) + ": " + fault_text(bad)).c_str());
+    flag_next = j[6] + j[1] * row_pitch(j[4]);
+    d_max = j[4] > d_max ? j[4] : d_max;
   }
   const int32_t row_cap = (int32_t)((2 * d_max + 2 + 63) / 64 * 64);
   const size_t lds_bytes = (size_t)kTile * 64 + (size_t)row_cap * sizeof(int32_t) + (size_t)row_cap + 64;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "mpc.h"
+#include "mpc_bandtrace.h"
 #include "mpc_device.h"
 #include "mpc_verify.h"
 
@@ -25,20 +26,9 @@ __attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
 
 namespace {
 using namespace mpc;
+using namespace mpc_band;
 
 constexpr uint32_t kNoColumn = 7;  // symbol slot of a step that carries no text column
-
-// A C G T -> 0..3 after upper-casing; any other byte -> `other` (4 on the query
-// side, 5 on the text side: equal to nothing)
-__device__ __forceinline__ uint32_t vcode(uint32_t c, uint32_t other) {
-  switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-  }
-  return other;
-}
 
 // lane l reads lane l - 1 (wave_shr:1 over the 64 lanes; lane 0 reads 0).  Must
 // run with every lane enabled: a disabled source lane reads as 0.
@@ -133,7 +123,9 @@ __global__ __launch_bounds__(64) void K_vscan(const uint8_t* __restrict__ seq, c
   const int64_t p = blockIdx.x;
   const int64_t q_off = pairs[4 * p], m64 = pairs[4 * p + 1], t_off = pairs[4 * p + 2], n = pairs[4 * p + 3];
   int32_t* o = out + 2 * p;
-  if (m64 < 1 || m64 > MPC_VERIFY_MAX_QUERY || n < 0 || q_off < 0 || t_off < 0) {  // (the host refuses these)
+  // restates check_pair of mpc_bandtrace.h, which the host applies before the launch (its n < 2^31 is not
+  // needed here: every loop bound is 64-bit)
+  if (m64 < 1 || m64 > MPC_VERIFY_MAX_QUERY || n < 0 || q_off < 0 || t_off < 0) {
     if (threadIdx.x == 0) { o[0] = -1; o[1] = -1; }
     return;
   }
@@ -160,15 +152,9 @@ extern "C" int mpc_verify_scan(const uint8_t* d_seq, const int64_t* d_pairs, int
   hipError_t e = hipMemcpyAsync(h.data(), d_pairs, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return mpc_fail_(MPC_E_HIP, (std::string("mpc_verify_scan: pair table: ") + hipGetErrorString(e)).c_str());
-  for (int32_t p = 0; p < n_pairs; ++p) {
-    const int64_t *r = &h[(size_t)p * 4], m = r[1], n = r[3];
-    std::string bad;
-    if (m < 1) bad = "empty query";
-    else if (m > MPC_VERIFY_MAX_QUERY) bad = "query of " + std::to_string(m) + " bases is longer than " + std::to_string(MPC_VERIFY_MAX_QUERY);
-    else if (n < 0 || n > INT32_MAX) bad = "text length " + std::to_string(n) + " is outside [0, 2^31)";
-    else if (r[0] < 0 || r[2] < 0) bad = "negative offset";
-    if (!bad.empty()) return mpc_fail_(MPC_E_ARG, ("mpc_verify_scan: pair " + std::to_string(p) + ": " + bad).c_str());
-  }
+  for (int32_t p = 0; p < n_pairs; ++p)
+    if (const int bad = check_pair(&h[(size_t)p * 4]))
+      return mpc_fail_(MPC_E_ARG, ("mpc_verify_scan: pair " + std::to_string(p) + ": " + fault_text(bad)).c_str());
   hipLaunchKernelGGL(K_vscan, dim3((unsigned)n_pairs), dim3(64), 0, st, d_seq, d_pairs, d_out);
   e = hipGetLastError();
   if (e != hipSuccess) return mpc_fail_(MPC_E_HIP, (std::string("K_vscan: ") + hipGetErrorString(e)).c_str());

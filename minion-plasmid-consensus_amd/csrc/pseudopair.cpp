@@ -120,8 +120,7 @@ int mpc_pseudopair(const char* paf_path, int64_t min_align_length, int has_min, 
   }
   const size_t L = starts.size();
   std::vector<Rec> recs(L);
-  int nt = n_threads > 0 ? n_threads : mpc_host::host_threads();
-  nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)nt, L / 4096 + 1));
+  const int nt = mpc_host::clamp_threads(n_threads, (long long)(L / 4096 + 1));
   std::vector<uint8_t> odd((size_t)nt, 0);  // bytes the parser declines
   auto work = [&](int t) {
     for (size_t i = L * t / nt; i < L * (t + 1) / nt; ++i) {

@@ -93,44 +93,81 @@ def _pack(pairs):
                 seqs.append(s)
                 off += len(s)
             tab[k, 2 * side], tab[k, 2 * side + 1] = where[id(s)], len(s)
-    seq = np.frombuffer(b"".join(seqs) + b"\0" * 8, np.uint8)
+    seq = np.frombuffer(b"".join(seqs) + b"\0" * 8, np.uint8).copy()  # (writable: torch takes no read-only array)
     return tab, seq
+
+
+def device_lib():
+    """libmpc.so with mpc_verify_scan bound."""
+    from . import engine
+    L = engine.lib()
+    if not hasattr(L, "_verify_ready"):
+        vp = ctypes.c_void_p
+        L.mpc_verify_scan.restype = ctypes.c_int
+        L.mpc_verify_scan.argtypes = [vp, vp, ctypes.c_int32, vp, vp]
+        L._verify_ready = True
+    return L
+
+
+def _device(device):
+    """(torch, torch.device) of a GPU; libmpc.so is loaded before torch is
+    imported: one HIP runtime in the process."""
+    from . import engine
+    device_lib()
+    import torch
+    if not torch.cuda.is_available():
+        raise engine.MpcError("no HIP device visible (use device='cpu' for the host path)")
+    return torch, torch.device("cuda", int(device))
+
+
+def _to_device(torch, dev, a):
+    a = np.ascontiguousarray(a)
+    d = torch.empty(a.nbytes, dtype=torch.uint8, device=dev)
+    if a.nbytes:
+        d.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8)))
+    return d
+
+
+def scan_table(seq, tab, device, threads=0, d_seq=None):
+    """int32 [n, 2] = (distance, end) of the pairs of an int64 [n, 4] pair
+    table {q_off, q_len, t_off, t_len} over the uint8 blob ``seq``:
+    mpc_verify_scan_host for device="cpu" (``threads``: 0 = all CPUs), else ONE
+    K_vscan launch (mpc_verify_scan) on that GPU.  ``d_seq``: the blob's device
+    copy when the caller has one."""
+    tab = np.ascontiguousarray(tab, np.int64).reshape(-1, 4)
+    n = len(tab)
+    out = np.zeros((n, 2), np.int32)
+    if n == 0:
+        return out
+    if device == "cpu":
+        L = host_lib()
+        if L.mpc_verify_scan_host(seq.ctypes.data, tab.ctypes.data, n, out.ctypes.data, threads) != 0:
+            raise VerifyError(L.mpc_verify_last_error().decode(errors="replace"))
+        return out
+    from . import engine
+    torch, dev = _device(device)
+    L = device_lib()
+    with torch.cuda.device(dev):
+        if d_seq is None:
+            d_seq = _to_device(torch, dev, seq)
+        d_tab = _to_device(torch, dev, tab)
+        d_out = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        engine._check(L.mpc_verify_scan(d_seq.data_ptr(), d_tab.data_ptr(), n, d_out.data_ptr(),
+                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return d_out.cpu().numpy().reshape(n, 2)
 
 
 def scan(pairs, device=0):
     """[(distance, end)] of every (expected, consensus) pair of bytes.  On a
-    GPU: one H2D copy of the packed table + sequences, one K_vscan launch, one
-    D2H copy of the results; device="cpu": the scalar host DP on all CPUs."""
+    GPU: H2D copies of the packed sequences and the pair table, one K_vscan
+    launch, one D2H copy of the results; device="cpu": the scalar host DP on
+    all CPUs."""
     pairs = [(bytes(q), bytes(t)) for q, t in pairs]  # (bytes(b) is b for a bytes object: shared sequences stay shared)
     _check_lengths(pairs)
     if not pairs:
         return []
     tab, seq = _pack(pairs)
-    n = len(pairs)
-    if device == "cpu":
-        L = host_lib()
-        out = np.zeros((n, 2), np.int32)
-        if L.mpc_verify_scan_host(seq.ctypes.data, tab.ctypes.data, n, out.ctypes.data, 0) != 0:
-            raise VerifyError(L.mpc_verify_last_error().decode(errors="replace"))
-        return [(int(d), int(e)) for d, e in out]
-    from . import engine
-    L = engine.lib()  # (before torch: one HIP runtime in the process)
-    import torch
-    if not torch.cuda.is_available():
-        raise engine.MpcError("no HIP device visible (use device='cpu' for the host scan)")
-    L.mpc_verify_scan.restype = ctypes.c_int
-    L.mpc_verify_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    dev = torch.device("cuda", int(device))
-    blob = np.concatenate([tab.reshape(-1).view(np.uint8), seq])
-    d_blob = torch.empty(len(blob), dtype=torch.uint8, device=dev)
-    d_blob.copy_(torch.from_numpy(blob))
-    d_out = torch.empty(2 * n, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev):
-        engine._check(L.mpc_verify_scan(d_blob.data_ptr() + tab.nbytes, d_blob.data_ptr(), n, d_out.data_ptr(),
-                                        ctypes.c_void_p(stream.cuda_stream)))
-        out = d_out.cpu().numpy().reshape(n, 2)
-    return [(int(d), int(e)) for d, e in out]
+    return [(int(d), int(e)) for d, e in scan_table(seq, tab, device)]
 
 
 def script(q, t, distance, end):

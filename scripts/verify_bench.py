@@ -54,12 +54,10 @@ def main():
 
     pkg = importlib.import_module("minion-plasmid-consensus_amd")
     v = pkg.verify
-    L = pkg.engine.lib()
+    L = v.device_lib()
     import torch
     if not torch.cuda.is_available():
         sys.exit("verify_bench.py measures on a GPU; none is visible")
-    L.mpc_verify_scan.restype = ctypes.c_int
-    L.mpc_verify_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     H = v.host_lib()
     dev = torch.device("cuda", args.device)
     results = []

@@ -262,3 +262,60 @@ def batches(cases):
             out.append((c["target"], c["max_error"], []))
         out[seen[key]][2].append((("%s_m%d_%d" % (c["kind"], c["m"], k)).encode(), c["read"]))
     return out
+
+
+# ---- one launch of the trace: shapes, job table, refused rows ---------------------
+
+def trace_shapes():
+    """[(note, oriented query, target, planted d or None)]"""
+    rng = np.random.default_rng(77)
+    out = []
+    # exactly d planted substitutions: W = 2 d + 1 inside, at and past one and two 64-lane rows
+    for d in (0, 1, 31, 32, 63, 64, 100):
+        q, t, _ = planted(rng, 700, d)
+        out.append(("subs d=%d" % d, q, t, d))
+    q, t, d = planted(rng, 700, 40, indels=True)
+    assert d == 40
+    out.append(("indels", q, t, d))
+    for m in (1, 63, 64, 65, 1000, 5000):
+        d = min(5, m // 16)
+        q, t, _ = planted(rng, m, d)
+        out.append(("m=%d" % m, q, t, d))
+    # bands cut by column 0 and by column n
+    q, t, d = planted(rng, 300, 20, left=0, right=30)
+    out.append(("column 0", q, t, 20))
+    q, t, d = planted(rng, 300, 20, left=30, right=0)
+    out.append(("column n", q, t, 20))
+    q, t, d = planted(rng, 300, 33, left=3, right=2, indels=True)
+    out.append(("both columns", q, t, None))
+    # n < m: the read hangs over both ends of the target
+    core = vu.rand_seq(rng, 260)
+    out.append(("n < m", vu.rand_seq(rng, 12) + core + vu.rand_seq(rng, 9), core, 21))
+    out.append(("n = 1", vu.rand_seq(rng, 5), b"G", None))
+    # minus strand: the oriented query is the reverse complement
+    q, t, _ = planted(rng, 500, 9)
+    out.append(("minus", revcomp(q), revcomp(t), 9))
+    out.append(("non-ACGT, lower case", vu.sprinkle(rng, q), vu.sprinkle(rng, t), None))
+    return out
+
+
+def job_table(tab, scan):
+    """int64 [n, 8] jobs of a pair table and its scan results, flag rows and runs back to back."""
+    jobs = np.zeros((len(tab), 8), np.int64)
+    jobs[:, :4] = tab
+    jobs[:, 4:6] = np.array(scan, np.int64)
+    pitch = (2 * jobs[:, 4] + 1 + 63) // 64 * 64
+    jobs[:, 6] = np.concatenate([[0], np.cumsum(jobs[:, 1] * pitch)[:-1]])
+    jobs[:, 7] = np.concatenate([[0], np.cumsum(2 * jobs[:, 4] + 1)[:-1]])
+    return jobs
+
+
+def refused_jobs(seq):
+    """(row, column, value) that each make the job table of trace_shapes() one the job rule refuses;
+    column 6 (flag_off) is the device entry point's part of the rule."""
+    return ((0, 1, 0), (0, 1, 65537), (1, 4, 4097), (1, 4, -1), (0, 5, -1), (0, 0, seq.nbytes), (3, 6, 0), (0, 6, -1), (0, 7, -1))
+
+
+def cigar_of(runs):
+    """The CIGAR (start -> end) of a read's runs (end -> start)."""
+    return "".join("%d%s" % (r >> 2, OPS[r & 3]) for r in reversed(runs))

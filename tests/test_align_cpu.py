@@ -180,6 +180,75 @@ def test_trace_host_flags_a_wrong_scan_result(al):
             al.trace(pk.seq, wrong, "cpu")
 
 
+# ---- one band trace and one table rule (csrc/mpc_bandtrace.h) ------------------------
+
+def test_host_trace_equals_verify_script(al):
+    """mpc_align_trace_host and mpc_verify_script are one band trace: on the
+    verify grid (n >= 1) the runs as a CIGAR, the start and the counts of the
+    one equal the cigar, start and counts of the other."""
+    pairs = [(q, t) for q, t in vu.small_pairs() if len(t) >= 1]
+    scan = vu.scan_host(pairs)
+    assert len(pairs) == 45 and max(d for d, _ in scan) <= vu.MAX_EDITS
+    seq, tab = vu.pack(pairs)
+    jobs = au.job_table(tab, scan)
+    rc, out, runs = al.trace(seq, jobs, "cpu", threads=3)
+    assert rc == 0
+    for k, ((q, t), (d, end)) in enumerate(zip(pairs, scan)):
+        src, start, counts, cigar = vu.script(q, t, d, end)
+        assert src == 0
+        got = runs[jobs[k, 7]: jobs[k, 7] + out[k, 6]].tolist()
+        assert (au.cigar_of(got), int(out[k, 1]), out[k, 2:6].tolist()) == (cigar, start, counts), (len(q), len(t))
+
+
+@pytest.fixture(scope="module")
+def traced(al):
+    """The GPU suite's launch traced on the host: blob, job table, out rows, runs."""
+    pairs = [(q, t) for _, q, t, _ in au.trace_shapes()]
+    seq, tab = vu.pack(pairs)
+    jobs = au.job_table(tab, vu.scan_host(pairs, 4))
+    rc, out, runs = al.trace(seq, jobs, "cpu")
+    assert rc == 0
+    return seq, jobs, out, runs
+
+
+def test_job_rule_refuses_and_names_the_row(al, traced):
+    """The rows the device entry point refuses before its launch: the host trace
+    and the renderer refuse the same ones and name the row; flag_off (column 6)
+    alone is the device's, the host keeps no workspace."""
+    seq, jobs, out, runs = traced
+    J = len(jobs)
+    render = lambda tab: al.render(seq, tab, np.zeros(J, np.uint8), out, runs, [b"r%d" % k for k in range(J)], b"tgt")
+    rows = au.refused_jobs(seq)
+    assert {col for _, col, _ in rows} == {0, 1, 4, 5, 6, 7}
+    for row, col, val in rows:
+        wrong = jobs.copy()
+        wrong[row, col] = val
+        if col == 6:
+            assert al.trace(seq, wrong, "cpu")[0] == 0
+            continue
+        with pytest.raises(al.AlignError, match="mpc_align_trace_host: read %d: " % row):
+            al.trace(seq, wrong, "cpu")
+        with pytest.raises(al.AlignError, match="mpc_align_render: read %d: " % row):
+            render(wrong)
+    assert len(render(jobs)[0]) > 0
+
+
+def test_revcomp_rule_refuses_and_names_the_row(al):
+    L = al.host_lib()
+    seq = np.frombuffer(b"ACGTACGTACGTACGT", np.uint8).copy()
+    good = [[0, 4, 8], [4, 4, 12], [0, 0, 0]]
+    tab = np.array(good, np.int64)
+    assert L.mpc_align_revcomp_host(seq.ctypes.data, seq.nbytes, tab.ctypes.data, 3, 1) == 0
+    assert bytes(seq) == b"ACGTACGTACGTACGT"  # (ACGT is its own reverse complement)
+    # a span outside the blob on either side, a negative length, source and destination overlapping
+    for row, bad in ((0, [-1, 4, 8]), (1, [4, 4, 13]), (2, [14, 4, 0]), (1, [4, -1, 12]), (2, [0, 4, 3]), (0, [2, 4, 0])):
+        tab = np.array(good, np.int64)
+        tab[row] = bad
+        assert L.mpc_align_revcomp_host(seq.ctypes.data, seq.nbytes, tab.ctypes.data, 3, 1) != 0, bad
+        assert b"mpc_align_revcomp_host: read %d: " % row in L.mpc_align_last_error()
+    assert bytes(seq) == b"ACGTACGTACGTACGT"  # refused before any byte is written
+
+
 # ---- the CLI ---------------------------------------------------------------------------
 
 def _write(path, text):

@@ -20,43 +20,10 @@ def al(pkg):
     return pkg.align
 
 
-def _shapes():
-    """[(note, oriented query, target, planted d or None)]"""
-    rng = np.random.default_rng(77)
-    out = []
-    # exactly d planted substitutions: W = 2 d + 1 inside, at and past one and two 64-lane rows
-    for d in (0, 1, 31, 32, 63, 64, 100):
-        q, t, _ = au.planted(rng, 700, d)
-        out.append(("subs d=%d" % d, q, t, d))
-    q, t, d = au.planted(rng, 700, 40, indels=True)
-    assert d == 40
-    out.append(("indels", q, t, d))
-    for m in (1, 63, 64, 65, 1000, 5000):
-        d = min(5, m // 16)
-        q, t, _ = au.planted(rng, m, d)
-        out.append(("m=%d" % m, q, t, d))
-    # bands cut by column 0 and by column n
-    q, t, d = au.planted(rng, 300, 20, left=0, right=30)
-    out.append(("column 0", q, t, 20))
-    q, t, d = au.planted(rng, 300, 20, left=30, right=0)
-    out.append(("column n", q, t, 20))
-    q, t, d = au.planted(rng, 300, 33, left=3, right=2, indels=True)
-    out.append(("both columns", q, t, None))
-    # n < m: the read hangs over both ends of the target
-    core = vu.rand_seq(rng, 260)
-    out.append(("n < m", vu.rand_seq(rng, 12) + core + vu.rand_seq(rng, 9), core, 21))
-    out.append(("n = 1", vu.rand_seq(rng, 5), b"G", None))
-    # minus strand: the oriented query is the reverse complement
-    q, t, _ = au.planted(rng, 500, 9)
-    out.append(("minus", au.revcomp(q), au.revcomp(t), 9))
-    out.append(("non-ACGT, lower case", vu.sprinkle(rng, q), vu.sprinkle(rng, t), None))
-    return out
-
-
 @pytest.fixture(scope="module")
 def launch(al):
     """The shapes as ONE launch: blob, job table, and the host's results."""
-    shapes = _shapes()
+    shapes = au.trace_shapes()
     pairs = [(q, t) for _, q, t, _ in shapes]
     seq, tab = vu.pack(pairs)
     scan = vu.scan_host(pairs, 4)
@@ -65,13 +32,7 @@ def launch(al):
             assert got == d, note  # d is what was planted ...
         if len(q) <= 1000:
             assert (got, end) == vu.score(q, t), note  # ... and what the numpy checker finds
-    jobs = np.zeros((len(pairs), 8), np.int64)
-    jobs[:, :4] = tab
-    jobs[:, 4:6] = np.array(scan, np.int64)
-    pitch = (2 * jobs[:, 4] + 1 + 63) // 64 * 64
-    need = jobs[:, 1] * pitch
-    jobs[:, 6] = np.concatenate([[0], np.cumsum(need)[:-1]])
-    jobs[:, 7] = np.concatenate([[0], np.cumsum(2 * jobs[:, 4] + 1)[:-1]])
+    jobs = au.job_table(tab, scan)
     rc, out, runs = al.trace(seq, jobs, "cpu")
     assert rc == 0
     return shapes, seq, jobs, out, runs
@@ -91,6 +52,18 @@ def test_trace_equals_host_in_one_launch(al, launch):
         if d is not None and note.startswith("subs"):  # the script holds exactly the planted substitutions
             assert out[k].tolist() == [0, 17, len(q) - d, d, 0, 0, out[k, 6], 0] and out[k, 6] <= 2 * d + 1
     assert np.array_equal(runs, host_runs)  # nothing outside a read's own runs either
+
+
+def test_trace_equals_verify_script(al, launch):
+    """K_atrace against verify's definition directly: its runs as a CIGAR, its
+    start and its counts are mpc_verify_script's for the same (d, end)."""
+    shapes, seq, jobs, _, _ = launch
+    rc, out, runs = al.trace(seq, jobs, 0)
+    assert rc == 0
+    for k, (note, q, t, _) in enumerate(shapes):
+        src, start, counts, cigar = vu.script(q, t, int(jobs[k, 4]), int(jobs[k, 5]))
+        assert src == 0, note
+        assert (au.cigar_of(_runs_of(jobs, out, runs, k)), int(out[k, 1]), out[k, 2:6].tolist()) == (cigar, start, counts), note
 
 
 def test_single_read_launch_equals_the_batch(al, launch):
@@ -127,7 +100,7 @@ def test_wrong_scan_result_sets_only_that_status(al, launch):
 
 def test_trace_refuses_bad_jobs_before_the_launch(al, pkg, launch):
     shapes, seq, jobs, _, _ = launch
-    for row, col, val in ((0, 1, 0), (0, 1, 65537), (1, 4, 4097), (1, 4, -1), (0, 5, -1), (0, 0, seq.nbytes), (3, 6, 0), (0, 6, -1), (0, 7, -1)):
+    for row, col, val in au.refused_jobs(seq):
         wrong = jobs.copy()
         wrong[row, col] = val
         with pytest.raises(pkg.engine.MpcError, match="mpc_align_trace: read"):

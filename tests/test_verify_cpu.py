@@ -119,6 +119,25 @@ def test_lengths_refused_host_side():
     assert v.scan([(b"ACGT", b"")], device="cpu") == [(4, 0)]
 
 
+def test_pair_rule_names_the_row():
+    """The refused lengths above, and a negative offset, in row 2 of a table
+    whose other rows are fine: the message names that row, nothing is written."""
+    L = vu.pkg().verify.host_lib()
+    seq = np.frombuffer(b"ACGTACGTACGTACGT", np.uint8).copy()
+    good = [[0, 4, 4, 8], [2, 3, 0, 0], [0, 1, 1, 15]]
+    bad = [[0, m, 0, n] for m, n in ((0, 4), (vu.MAX_QUERY + 1, 4), (4, -1), (4, 2 ** 31))] + [[-1, 4, 4, 8], [0, 4, -4, 8]]
+    for row in bad:
+        tab = np.array(good[:2] + [row] + good[2:], np.int64)
+        out = np.full((4, 2), -7, np.int32)
+        assert L.mpc_verify_scan_host(seq.ctypes.data, tab.ctypes.data, 4, out.ctypes.data, 2) != 0, row
+        assert b"mpc_verify_scan_host: pair 2: " in L.mpc_verify_last_error()
+        assert (out == -7).all()
+    tab = np.array(good, np.int64)
+    out = np.full((3, 2), -7, np.int32)
+    assert L.mpc_verify_scan_host(seq.ctypes.data, tab.ctypes.data, 3, out.ctypes.data, 2) == 0
+    assert out.tolist() == [[0, 4], [3, 0], [0, 4]]
+
+
 def test_read_expected(tmp_path):
     v = vu.pkg().verify
     p = tmp_path / "e.fa"
