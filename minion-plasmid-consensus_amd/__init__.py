@@ -3,7 +3,9 @@ scottdbrown/minion-plasmid-consensus (src/mapped_paf_read_parser.py).
 
 Modules
   ingest   Steps 1-3 (FASTA / PAF ingest, flanks) -> packed per-read arrays
-  engine   ctypes binding of libmpc.so (include/mpc.h) + torch device buffers
+  _native  the ctypes prototype of every function of include/*.h, applied when a
+           library is loaded; the tools' shared device plumbing
+  engine   libmpc.so (include/mpc.h): its loading rules + torch device buffers
   writers  Step 7 output files
   synth    seeded synthetic cs-tagged data (tests / bench)
   dist     multi-GPU read sharding over RCCL (torch.distributed)

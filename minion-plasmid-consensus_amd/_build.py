@@ -8,6 +8,12 @@ the repo snapshot to the GPU box).
   libmpc_ingest.so native host I/O: ingest (Steps 1-3) and writers (Step 7) (include/mpc_ingest.h, g++ -pthread)
                    and the host halves of verify_consensus (include/mpc_verify.h), coverage_qc (mpc_coverage.h)
                    linkage_qc (mpc_linkage.h) and align_reads (mpc_align.h)
+
+Shared glue, listed below so that a change to it makes its library stale:
+csrc/mpc_launch.h (the launchers of the four tool .hip files) in HIP_HEADERS,
+csrc/host_file.h (the host parsers' file mapping, line cuts, digit loop and
+last-error message) in INGEST_HEADERS.  The ctypes prototypes of both
+libraries are in _native.py.
 """
 import os
 import subprocess
@@ -24,11 +30,12 @@ LIBINGEST = os.path.join(PKG, "libmpc_ingest.so")
 HIP_SOURCES = ["mpc_kernels.hip", "mpc_verify.hip", "mpc_cov.hip", "mpc_link.hip", "mpc_align.hip"]
 HOST_SOURCES = ["mpc_plan.cpp"]  # libmpc.so's host planner (g++, no HIP)
 HIP_HEADERS = ["mpc_device.h", "mpc_geometry.h", "mpc_plan.h", "mpc_cswalk.h", "mpc_cstables.h", "mpc_bandtrace.h",
+               "mpc_launch.h",  # the launchers' host glue of the four tool .hip files
                # the stages of mpc_kernels.hip (one translation unit), in pipeline order
                "mpc_k_common.h", "mpc_k_parse.h", "mpc_k_index.h", "mpc_k_left.h", "mpc_k_wrap.h", "mpc_k_layout.h",
                "mpc_k_rows.h", "mpc_k_call.h"]
 INGEST_SOURCES = ["ingest.cpp", "writers.cpp", "pseudopair.cpp", "verify.cpp", "coverage.cpp", "linkage.cpp", "align.cpp"]
-INGEST_HEADERS = ["host_threads.h", "mpc_cswalk_host.h", "mpc_cstables.h", "mpc_bandtrace.h"]  # csrc headers of libmpc_ingest.so
+INGEST_HEADERS = ["host_threads.h", "host_file.h", "mpc_cswalk_host.h", "mpc_cstables.h", "mpc_bandtrace.h"]  # csrc headers of libmpc_ingest.so
 
 
 def _stale(target, sources):

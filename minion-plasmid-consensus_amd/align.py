@@ -20,8 +20,8 @@ import ctypes
 
 import numpy as np
 
-from . import verify
-from .verify import _device, _to_device  # (the scan's device plumbing: libmpc.so before torch)
+from . import _native, verify
+from .verify import _to_device
 
 MAX_QUERY = 65536                 # mpc_verify.h MPC_VERIFY_MAX_QUERY
 MAX_EDITS = 4096                  # mpc_align.h MPC_ALIGN_MAX_EDITS
@@ -90,42 +90,15 @@ def read_batches(path, batch_bases=DEFAULT_BATCH_BASES):
 # ---- native bindings -----------------------------------------------------------
 
 def host_lib():
-    """libmpc_ingest.so with the align entry points bound."""
-    try:
-        L = verify.host_lib()
-    except verify.VerifyError as e:
-        raise AlignError(str(e))
-    if not hasattr(L, "_align_ready"):
-        vp, i32, i64, ci = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
-        L.mpc_align_revcomp_host.restype = ci
-        L.mpc_align_revcomp_host.argtypes = [vp, i64, vp, i32, ci]
-        L.mpc_align_plan.restype = ci
-        L.mpc_align_plan.argtypes = [vp, vp, i32, ctypes.c_double, i64, vp, vp, ctypes.POINTER(i32)]
-        L.mpc_align_trace_host.restype = ci
-        L.mpc_align_trace_host.argtypes = [vp, i64, vp, i32, vp, vp, i64, ci]
-        L.mpc_align_render.restype = ci
-        L.mpc_align_render.argtypes = [vp, i64, vp, i32, vp, vp, vp, i64, vp, vp, ctypes.c_char_p, vp, i64, vp,
-                                       ctypes.POINTER(i64), ci]
-        L.mpc_align_last_error.restype = ctypes.c_char_p
-        L._align_ready = True
-    return L
+    """libmpc_ingest.so (its prototypes: _native.host_prototypes)."""
+    return _native.host(AlignError)
 
 
 def _host_error(L):
     return L.mpc_align_last_error().decode(errors="replace")
 
 
-def device_lib():
-    """libmpc.so with the align entry points bound (the scan's: verify.device_lib)."""
-    L = verify.device_lib()
-    if not hasattr(L, "_align_ready"):
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        L.mpc_align_revcomp.restype = ctypes.c_int
-        L.mpc_align_revcomp.argtypes = [vp, i64, vp, i32, vp]
-        L.mpc_align_trace.restype = ctypes.c_int
-        L.mpc_align_trace.argtypes = [vp, i64, vp, i32, vp, i64, vp, vp, i64, vp]
-        L._align_ready = True
-    return L
+device_lib = verify.device_lib
 
 
 # ---- the steps, one batch at a time --------------------------------------------
@@ -174,10 +147,10 @@ def orient_and_scan(pk, device=0, threads=0):
             raise AlignError(_host_error(L))
     else:
         from . import engine
-        torch, dev = _device(device)
+        torch, dev = _native.device(device, "host path")
         L = device_lib()
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _native.stream_ptr(torch, dev)
             pk.d_seq = _to_device(torch, dev, pk.seq)
             d_tab = _to_device(torch, dev, rc_tab)
             engine._check(L.mpc_align_revcomp(pk.d_seq.data_ptr(), pk.seq.nbytes, d_tab.data_ptr(), R, stream))
@@ -238,12 +211,12 @@ def trace(seq, jobs, device=0, threads=0, d_seq=None, workspace=None):
             raise AlignError(_host_error(L))
         return rc, out, runs[:runs_cap]
     from . import engine
-    torch, dev = _device(device)
+    torch, dev = _native.device(device, "host path")
     L = device_lib()
     pitch = (2 * jobs[:, 4] + 1 + 63) // 64 * 64
     flags_bytes = max(int((jobs[:, 6] + jobs[:, 1] * pitch).max()), 64)
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _native.stream_ptr(torch, dev)
         if d_seq is None:
             d_seq = _to_device(torch, dev, seq)
         ws = workspace if workspace is not None else {}

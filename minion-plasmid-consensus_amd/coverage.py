@@ -22,6 +22,8 @@ import math
 
 import numpy as np
 
+from . import _native
+
 STATS = 16  # mpc_coverage.h MPC_COV_STATS
 (ST_RECORDS, ST_MATCH, ST_MISMATCH, ST_INS_EVENTS, ST_INS_BASES, ST_DEL_EVENTS, ST_DEL_BASES, ST_SUM, ST_SUMSQ,
  ST_MIN, ST_MAX, ST_BELOW, ST_SUM_DELETED) = range(13)
@@ -45,35 +47,14 @@ class _Paf(ctypes.Structure):
 
 
 def host_lib():
-    """libmpc_ingest.so with the coverage entry points bound."""
-    from . import ingest
-    L = ingest._native()
-    if L is None:
-        raise CoverageError("libmpc_ingest.so is missing and cannot be built (no host compiler)")
-    if not hasattr(L, "_coverage_ready"):
-        vp = ctypes.c_void_p
-        L.mpc_coverage_host.restype = ctypes.c_int
-        L.mpc_coverage_host.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_uint32,
-                                        vp, vp, vp, ctypes.c_int, vp]
-        L.mpc_coverage_ingest.restype = ctypes.c_int
-        L.mpc_coverage_ingest.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_Paf)]
-        L.mpc_coverage_ingest_free.argtypes = [ctypes.POINTER(_Paf)]
-        L.mpc_coverage_last_error.restype = ctypes.c_char_p
-        L._coverage_ready = True
-    return L
+    """libmpc_ingest.so (its prototypes: _native.host_prototypes)."""
+    return _native.host(CoverageError)
 
 
 def _device_lib():
+    """libmpc.so (its prototypes: _native.device_prototypes)."""
     from . import engine
-    L = engine.lib()  # (before torch: one HIP runtime in the process)
-    if not hasattr(L, "_coverage_ready"):
-        vp = ctypes.c_void_p
-        L.mpc_coverage_run.restype = ctypes.c_int
-        L.mpc_coverage_run.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.c_uint32,
-                                       vp, vp, vp, vp]
-        L.mpc_coverage_tile_bytes.restype = ctypes.c_int
-        L._coverage_ready = True
-    return L
+    return engine.lib()
 
 
 def tile_bytes():
@@ -184,21 +165,16 @@ def run(cs, cs_off, tstart, rec_sample, lengths, regions=None, min_depth=0, devi
             raise CoverageError(L.mpc_coverage_last_error().decode(errors="replace"))
     else:
         from . import engine
-        L = _device_lib()
-        import torch
-        if not torch.cuda.is_available():
-            raise engine.MpcError("no HIP device visible (use device='cpu' for the host walk)")
-        dev = torch.device("cuda", int(device))
+        torch, dev = _native.device(device)
         with torch.cuda.device(dev):
             # the int64 tables first, then rec_sample, then the cs bytes
             at, d_blob = upload(torch, dev, [cs_off, tstart, pos_off, region.reshape(-1), rec_sample, cs])
             d_rows = torch.empty((n_pos, 4), dtype=torch.int32, device=dev)
             d_stats = torch.empty((S, STATS), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            engine._check(L.mpc_coverage_run(at[5], at[0], at[1], at[4], n, at[2], at[3], S, min_depth,
-                                             d_rows.data_ptr(), d_stats.data_ptr(), d_status.data_ptr(),
-                                             ctypes.c_void_p(stream.cuda_stream)))
+            engine._check(engine.lib().mpc_coverage_run(at[5], at[0], at[1], at[4], n, at[2], at[3], S, min_depth,
+                                                        d_rows.data_ptr(), d_stats.data_ptr(), d_status.data_ptr(),
+                                                        _native.stream_ptr(torch, dev)))
             status = d_status.cpu().numpy()
             rows = d_rows.cpu().numpy().view(np.uint32)
             stats = d_stats.cpu().numpy().view(np.uint64)

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "host_file.h"
 #include "host_threads.h"
 #include "mpc_align.h"
 #include "mpc_bandtrace.h"
@@ -22,13 +23,9 @@ namespace {
 using namespace mpc_band;
 using mpc_host::clamp_threads;
 
-constexpr int kOk = 0, kArg = -1;  // MPC_OK, MPC_E_ARG of mpc.h
+constexpr int kOk = 0;  // MPC_OK of mpc.h
 
-thread_local std::string g_aerr;
-int afail(const std::string& msg, int code = kArg) {
-  g_aerr = msg;
-  return code;
-}
+thread_local mpc_host::LastError g_aerr;
 
 inline char lower(uint8_t c) { return (char)((c >= 'A' && c <= 'Z') ? c + 32 : c); }
 
@@ -102,15 +99,15 @@ void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool min
 
 }  // namespace
 
-extern "C" const char* mpc_align_last_error(void) { return g_aerr.c_str(); }
+extern "C" const char* mpc_align_last_error(void) { return g_aerr.msg.c_str(); }
 
 extern "C" int mpc_align_revcomp_host(uint8_t* seq, int64_t seq_bytes, const int64_t* tab, int32_t n_reads, int threads) {
-  if (n_reads < 0) return afail("mpc_align_revcomp_host: n_reads < 0");
+  if (n_reads < 0) return g_aerr.fail("mpc_align_revcomp_host: n_reads < 0");
   if (n_reads == 0) return kOk;
-  if (!seq || !tab) return afail("mpc_align_revcomp_host: null pointer");
+  if (!seq || !tab) return g_aerr.fail("mpc_align_revcomp_host: null pointer");
   for (int32_t r = 0; r < n_reads; ++r)
     if (const int bad = check_revcomp(tab + 3 * (int64_t)r, seq_bytes))
-      return afail("mpc_align_revcomp_host: read " + std::to_string(r) + ": " + fault_text(bad));
+      return g_aerr.fail("mpc_align_revcomp_host: read " + std::to_string(r) + ": " + fault_text(bad));
   const int nt = clamp_threads(threads, n_reads);
   std::atomic<int32_t> next{0};
   mpc_host::parallel(nt, [&](int) {
@@ -125,9 +122,9 @@ extern "C" int mpc_align_revcomp_host(uint8_t* seq, int64_t seq_bytes, const int
 
 extern "C" int mpc_align_plan(const int32_t* scan, const int32_t* lens, int32_t n_reads, double max_error,
                               int64_t workspace_bytes, int64_t* plan, int32_t* cuts, int32_t* n_launches) {
-  if (n_reads < 0) return afail("mpc_align_plan: n_reads < 0");
-  if (!n_launches || !cuts || (n_reads > 0 && (!scan || !lens || !plan))) return afail("mpc_align_plan: null pointer");
-  if (!(max_error >= 0.0) || workspace_bytes < 0) return afail("mpc_align_plan: max_error or workspace_bytes < 0");
+  if (n_reads < 0) return g_aerr.fail("mpc_align_plan: n_reads < 0");
+  if (!n_launches || !cuts || (n_reads > 0 && (!scan || !lens || !plan))) return g_aerr.fail("mpc_align_plan: null pointer");
+  if (!(max_error >= 0.0) || workspace_bytes < 0) return g_aerr.fail("mpc_align_plan: max_error or workspace_bytes < 0");
   int32_t nl = 0;
   int64_t flag_off = 0, run_off = 0;
   bool open = false;  // the current launch holds a mapped read
@@ -136,8 +133,8 @@ extern "C" int mpc_align_plan(const int32_t* scan, const int32_t* lens, int32_t 
     const int32_t* s = scan + 4 * (int64_t)r;
     int64_t* p = plan + 8 * (int64_t)r;
     const int64_t m = lens[r];
-    if (m < 1 || m > MPC_VERIFY_MAX_QUERY) return afail("mpc_align_plan: read " + std::to_string(r) + ": length outside [1, 65536]");
-    if (s[0] < 0 || s[2] < 0 || s[1] < 0 || s[3] < 0) return afail("mpc_align_plan: read " + std::to_string(r) + ": negative scan result");
+    if (m < 1 || m > MPC_VERIFY_MAX_QUERY) return g_aerr.fail("mpc_align_plan: read " + std::to_string(r) + ": length outside [1, 65536]");
+    if (s[0] < 0 || s[2] < 0 || s[1] < 0 || s[3] < 0) return g_aerr.fail("mpc_align_plan: read " + std::to_string(r) + ": negative scan result");
     const bool minus = s[2] < s[0];  // a tie is '+'
     const int64_t d = minus ? s[2] : s[0], end = minus ? s[3] : s[1];
     const double lim = std::floor(max_error * (double)m);
@@ -147,7 +144,7 @@ extern "C" int mpc_align_plan(const int32_t* scan, const int32_t* lens, int32_t 
     if (!mapped) continue;
     const int64_t need = m * row_pitch(d);
     if (need > workspace_bytes)
-      return afail("mpc_align_plan: read " + std::to_string(r) + " needs " + std::to_string(need) +
+      return g_aerr.fail("mpc_align_plan: read " + std::to_string(r) + " needs " + std::to_string(need) +
                    " flag bytes, the workspace budget is " + std::to_string(workspace_bytes));
     if (open && flag_off + need > workspace_bytes) {  // close the launch before this read
       cuts[++nl] = r;
@@ -167,12 +164,12 @@ extern "C" int mpc_align_plan(const int32_t* scan, const int32_t* lens, int32_t 
 
 extern "C" int mpc_align_trace_host(const uint8_t* seq, int64_t seq_bytes, const int64_t* jobs, int32_t n_jobs,
                                     int32_t* out, int32_t* runs, int64_t runs_cap, int threads) {
-  if (n_jobs < 0) return afail("mpc_align_trace_host: n_jobs < 0");
+  if (n_jobs < 0) return g_aerr.fail("mpc_align_trace_host: n_jobs < 0");
   if (n_jobs == 0) return kOk;
-  if (!seq || !jobs || !out || !runs) return afail("mpc_align_trace_host: null pointer");
+  if (!seq || !jobs || !out || !runs) return g_aerr.fail("mpc_align_trace_host: null pointer");
   for (int32_t r = 0; r < n_jobs; ++r)
     if (const int bad = check_job(jobs + 8 * (int64_t)r, seq_bytes, runs_cap))
-      return afail("mpc_align_trace_host: read " + std::to_string(r) + ": " + fault_text(bad));
+      return g_aerr.fail("mpc_align_trace_host: read " + std::to_string(r) + ": " + fault_text(bad));
   const int nt = clamp_threads(threads, n_jobs);
   std::atomic<int32_t> next{0};
   std::atomic<int> oom{0};
@@ -188,10 +185,10 @@ extern "C" int mpc_align_trace_host(const uint8_t* seq, int64_t seq_bytes, const
       }
     }
   });
-  if (oom) return afail("mpc_align_trace_host: out of memory for a band");
+  if (oom) return g_aerr.fail("mpc_align_trace_host: out of memory for a band");
   for (int32_t r = 0; r < n_jobs; ++r)
     if (out[8 * (int64_t)r] != MPC_ALIGN_OK)
-      return afail("mpc_align_trace_host: read " + std::to_string(r) + ": the band does not give the scan's distance at (m, end)",
+      return g_aerr.fail("mpc_align_trace_host: read " + std::to_string(r) + ": the band does not give the scan's distance at (m, end)",
                    MPC_ALIGN_E_SCAN);
   return kOk;
 }
@@ -200,12 +197,12 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
                                 const uint8_t* strand, const int32_t* out, const int32_t* runs, int64_t runs_cap,
                                 const char* names, const int64_t* name_off, const char* tname, char* buf, int64_t buf_cap,
                                 int64_t* line_len, int64_t* written, int threads) {
-  if (n_jobs < 0) return afail("mpc_align_render: n_jobs < 0");
-  if (!written) return afail("mpc_align_render: null pointer");
+  if (n_jobs < 0) return g_aerr.fail("mpc_align_render: n_jobs < 0");
+  if (!written) return g_aerr.fail("mpc_align_render: null pointer");
   *written = 0;
   if (n_jobs == 0) return kOk;
   if (!seq || !jobs || !strand || !out || !runs || !names || !name_off || !tname || !line_len || (!buf && buf_cap > 0))
-    return afail("mpc_align_render: null pointer");
+    return g_aerr.fail("mpc_align_render: null pointer");
   for (int32_t r = 0; r < n_jobs; ++r) {
     const int64_t* j = jobs + 8 * (int64_t)r;
     const int32_t* o = out + 8 * (int64_t)r;
@@ -213,7 +210,7 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
     if (!bad && o[0] != MPC_ALIGN_OK) bad = "status is not MPC_ALIGN_OK";
     if (!bad && (o[6] < 0 || o[6] > 2 * j[4] + 1 || o[1] < 0 || o[1] > j[5])) bad = "trace output outside its bounds";
     if (!bad && name_off[r + 1] < name_off[r]) bad = "name offsets descend";
-    if (bad) return afail("mpc_align_render: read " + std::to_string(r) + ": " + bad);
+    if (bad) return g_aerr.fail("mpc_align_render: read " + std::to_string(r) + ": " + bad);
     // the runs must walk exactly the read and the target span (they index both sequences)
     int64_t qn = 0, tn = 0;
     for (int32_t k = 0; k < o[6]; ++k) {
@@ -222,7 +219,7 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
       if (op != kOpI) qn += len;
       if (op != kOpD) tn += len;
     }
-    if (qn != j[1] || tn != j[5] - o[1]) return afail("mpc_align_render: read " + std::to_string(r) + ": runs do not span the read");
+    if (qn != j[1] || tn != j[5] - o[1]) return g_aerr.fail("mpc_align_render: read " + std::to_string(r) + ": runs do not span the read");
   }
   // contiguous shares of reads per thread, joined in order
   const int nt = clamp_threads(threads, n_jobs);
@@ -241,7 +238,7 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
   int64_t total = 0;
   for (const std::string& s : part) total += (int64_t)s.size();
   *written = total;
-  if (total > buf_cap) return afail("mpc_align_render: the buffer holds " + std::to_string(buf_cap) + " bytes, the lines need " + std::to_string(total));
+  if (total > buf_cap) return g_aerr.fail("mpc_align_render: the buffer holds " + std::to_string(buf_cap) + " bytes, the lines need " + std::to_string(total));
   int64_t at = 0;
   for (const std::string& s : part) {
     std::memcpy(buf + at, s.data(), s.size());

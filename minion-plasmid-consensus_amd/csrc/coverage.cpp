@@ -4,11 +4,6 @@
 //                        timing baseline, --device cpu
 //   mpc_coverage_ingest  memory-mapped, multi-threaded PAF read: target, span,
 //                        mapq, read length, strand and the cs bytes per kept line
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -19,6 +14,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "host_file.h"
 #include "host_threads.h"
 #include "mpc_coverage.h"
 #include "mpc_cstables.h"
@@ -28,13 +24,9 @@ namespace {
 
 using sv = std::string_view;
 
-constexpr int kOk = 0, kArg = -1;  // MPC_OK, MPC_E_ARG of mpc.h
+constexpr int kOk = 0;  // MPC_OK of mpc.h
 
-thread_local std::string g_cerr;
-int cfail(const std::string& msg) {
-  g_cerr = msg;
-  return kArg;
-}
+thread_local mpc_host::LastError g_cerr;
 
 using mpc_host::parallel;
 
@@ -60,39 +52,10 @@ struct RowFx {
 
 // ---------------------------------------------------------------- PAF ingest
 
-struct Mapped {
-  const char* p = "";
-  size_t n = 0;
-  void* m = nullptr;
-  int fd = -1;
-  Mapped() = default;
-  Mapped(const Mapped&) = delete;
-  ~Mapped() {
-    if (m && m != MAP_FAILED) munmap(m, n);
-    if (fd >= 0) close(fd);
-  }
-  bool open(const char* path) {
-    fd = ::open(path, O_RDONLY);
-    if (fd < 0) return false;
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return false;
-    n = (size_t)st.st_size;
-    if (n == 0) return true;
-    m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) return false;
-    madvise(m, n, MADV_SEQUENTIAL);
-    p = static_cast<const char*>(m);
-    return true;
-  }
-};
-
+// Policy: digits only (1-18 of them); anything else refuses the line.
 bool plain_int(sv s, int64_t* out) {
-  if (s.empty() || s.size() > 18) return false;
-  int64_t v = 0;
-  for (char c : s) {
-    if (c < '0' || c > '9') return false;
-    v = v * 10 + (c - '0');
-  }
+  int64_t v;
+  if (s.empty() || s.size() > 18 || mpc_host::leading_digits(s, &v) != s.size()) return false;
   *out = v;
   return true;
 }
@@ -159,19 +122,19 @@ int ingest_fail(mpc_coverage_paf* out, const std::string& msg) {
 
 extern "C" {
 
-const char* mpc_coverage_last_error(void) { return g_cerr.c_str(); }
+const char* mpc_coverage_last_error(void) { return g_cerr.msg.c_str(); }
 
 int mpc_coverage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* tstart, const int32_t* rec_sample,
                       int64_t n_records, const int64_t* pos_off, const int64_t* region, int32_t n_samples,
                       uint32_t min_depth, uint32_t* rows, uint64_t* stats, int32_t* status, int threads,
                       int64_t* rec_out) {
-  if (n_records < 0 || n_records > INT32_MAX) return cfail("mpc_coverage_host: n_records outside [0, 2^31)");
-  if (n_samples < 1) return cfail("mpc_coverage_host: n_samples < 1");
+  if (n_records < 0 || n_records > INT32_MAX) return g_cerr.fail("mpc_coverage_host: n_records outside [0, 2^31)");
+  if (n_samples < 1) return g_cerr.fail("mpc_coverage_host: n_samples < 1");
   if (!pos_off || !region || !rows || !stats || !status || !cs_off || (n_records > 0 && (!cs || !tstart || !rec_sample)))
-    return cfail("mpc_coverage_host: null pointer");
+    return g_cerr.fail("mpc_coverage_host: null pointer");
   const size_t S = (size_t)n_samples;
   const std::string bad = mpc_host::check_samples(pos_off, region, S);
-  if (!bad.empty()) return cfail("mpc_coverage_host: " + bad);
+  if (!bad.empty()) return g_cerr.fail("mpc_coverage_host: " + bad);
   const size_t n_words = (size_t)pos_off[S] * 4;
   std::fill(rows, rows + n_words, 0u);
   std::fill(stats, stats + S * MPC_COV_STATS, (uint64_t)0);
@@ -254,18 +217,13 @@ int mpc_coverage_ingest(const char* paf_path, int mode, int n_threads, mpc_cover
   memset(out, 0, sizeof(*out));
   if (!paf_path) return ingest_fail(out, "no PAF path");
   if (mode != 0 && mode != 1) return ingest_fail(out, "mode is neither 0 (first alignment per read) nor 1 (all)");
-  Mapped f;
-  if (!f.open(paf_path)) return ingest_fail(out, std::string(paf_path) + ": cannot be read");
+  mpc_host::Mapped f;
+  if (!f.open(paf_path, true)) return ingest_fail(out, std::string(paf_path) + ": cannot be read");
   const int T = mpc_host::clamp_threads(n_threads, (long long)(f.n / (1 << 16) + 1));
 
-  // cuts at line starts
+  // cuts at line starts (ascending: n k / T and line_start_at_or_after are both monotone)
   std::vector<size_t> cut((size_t)T + 1, f.n);
-  cut[0] = 0;
-  for (int k = 1; k < T; ++k) {
-    size_t a = std::max(f.n * (size_t)k / T, cut[(size_t)k - 1]);
-    while (a < f.n && a > 0 && f.p[a - 1] != '\n') ++a;
-    cut[(size_t)k] = a;
-  }
+  for (int k = 0; k < T; ++k) cut[(size_t)k] = mpc_host::line_start_at_or_after(f.p, f.n, f.n * (size_t)k / T);
   std::vector<std::vector<Line>> part((size_t)T);
   std::vector<int64_t> bad_line((size_t)T, -1);  // local index of the first bad line
   std::vector<const char*> bad_why((size_t)T, nullptr);

@@ -18,12 +18,10 @@
 // all cores: PAF lines and FASTA records are independent, only the PAF dedup
 // (file order) is sequential.
 #include "mpc_ingest.h"
+#include "host_file.h"
 #include "host_threads.h"
 
-#include <fcntl.h>
 #include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <emmintrin.h>
 
 #include <algorithm>
@@ -43,34 +41,8 @@ namespace {
 
 using sv = std::string_view;
 
-struct Mapped {
-  const char* p = "";
-  size_t n = 0;
-  void* m = nullptr;
-  int fd = -1;
-  Mapped() = default;
-  Mapped(const Mapped&) = delete;
-  Mapped(Mapped&& o) noexcept : p(o.p), n(o.n), m(o.m), fd(o.fd) {
-    o.p = ""; o.n = 0; o.m = nullptr; o.fd = -1;
-  }
-  ~Mapped() {
-    if (m && m != MAP_FAILED) munmap(m, n);
-    if (fd >= 0) close(fd);
-  }
-  bool open(const char* path) {
-    fd = ::open(path, O_RDONLY);
-    if (fd < 0) return false;
-    struct stat st;
-    if (fstat(fd, &st) != 0) return false;
-    n = (size_t)st.st_size;
-    if (n == 0) return true;
-    m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) return false;
-    madvise(m, n, MADV_SEQUENTIAL);
-    p = static_cast<const char*>(m);
-    return true;
-  }
-};
+using mpc_host::line_start_at_or_after;
+using mpc_host::Mapped;
 
 // str.isspace() restricted to ASCII (what rstrip() removes)
 inline bool py_space(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x1f); }
@@ -171,31 +143,18 @@ inline PafClasses classify_paf64(const char* p, size_t n) {
   return m;
 }
 
-// [a, b) moved forward to line starts (a line = up to and including '\n'; a last
-// line without '\n' counts)
-inline size_t line_start_at_or_after(const Mapped& f, size_t x) {
-  if (x == 0) return 0;
-  if (x >= f.n) return f.n;
-  const void* nl = memchr(f.p + x - 1, '\n', f.n - (x - 1));
-  return nl ? (size_t)(static_cast<const char*>(nl) - f.p) + 1 : f.n;
-}
-
-// Python int() of a plain decimal field: [-]digits.  0 = ok, 1 = not an int for
-// Python either (empty, stray chars), 2 = let Python decide (sign '+', spaces,
-// '_', very long)
+// Policy: Python int() of a plain decimal field, [-]digits.  0 = ok, 1 = not an
+// int for Python either (empty, stray chars), 2 = let Python decide (sign '+',
+// spaces, '_', very long)
 int plain_int(sv s, int64_t* out) {
   if (s.empty()) return 1;
-  size_t i = 0;
-  bool neg = false;
-  if (s[0] == '-') { neg = true; i = 1; }
-  if (i >= s.size()) return 1;
-  if (s.size() - i > 18) return 2;
-  int64_t v = 0;
-  for (; i < s.size(); ++i) {
-    const char c = s[i];
-    if (c < '0' || c > '9') return (c == '+' || c == '_' || py_space((unsigned char)c)) ? 2 : 1;
-    v = v * 10 + (c - '0');
-  }
+  const bool neg = s[0] == '-';
+  const sv d = s.substr(neg ? 1 : 0);
+  if (d.empty()) return 1;
+  if (d.size() > 18) return 2;
+  int64_t v;
+  const size_t k = mpc_host::leading_digits(d, &v);
+  if (k < d.size()) return (d[k] == '+' || d[k] == '_' || py_space((unsigned char)d[k])) ? 2 : 1;
   *out = neg ? -v : v;
   return 0;
 }
@@ -362,7 +321,8 @@ void job_ref_paf(Job& J, int T) {
   // parse_paf_line for the reference's exact error.
   std::atomic<bool> py{false};
   parallel(T, [&](int k) {
-    const size_t a = line_start_at_or_after(fp, fp.n * k / T), b = line_start_at_or_after(fp, fp.n * (k + 1) / T);
+    // [a, b) moved forward to line starts (a last line without '\n' counts)
+    const size_t a = line_start_at_or_after(fp.p, fp.n, fp.n * k / T), b = line_start_at_or_after(fp.p, fp.n, fp.n * (k + 1) / T);
     size_t tabs[8];
     int ntab = 0;
     size_t cs0 = SIZE_MAX, cs1 = SIZE_MAX;  // the cs field's value [cs0, cs1) (cs1: the next tab)
@@ -501,7 +461,7 @@ bool jobs_fasta(std::vector<Job>& jobs, const Mapped& fa, int T) {
   std::vector<std::vector<Fail>> ffails((size_t)nj, std::vector<Fail>((size_t)T));
   std::atomic<bool> py{false};
   auto rec_start = [&](size_t x) {  // first header line ('>' at a line start) at or after x
-    size_t y = line_start_at_or_after(fa, x);
+    size_t y = line_start_at_or_after(fa.p, fa.n, x);
     while (y < fa.n && fa.p[y] != '>') {
       const char* nl = static_cast<const char*>(memchr(fa.p + y, '\n', fa.n - y));
       y = nl ? (size_t)(nl - fa.p) + 1 : fa.n;

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "host_file.h"
 #include "host_threads.h"
 #include "mpc_coverage.h"
 #include "mpc_cstables.h"
@@ -18,13 +19,9 @@
 
 namespace {
 
-constexpr int kOk = 0, kArg = -1;  // MPC_OK, MPC_E_ARG of mpc.h
+constexpr int kOk = 0;  // MPC_OK of mpc.h
 
-thread_local std::string g_lerr;
-int lfail(const std::string& msg) {
-  g_lerr = msg;
-  return kArg;
-}
+thread_local mpc_host::LastError g_lerr;
 
 using mpc_host::parallel;
 
@@ -101,13 +98,13 @@ void count_pairs(const uint8_t* alleles, int64_t N, int K, uint32_t* pair, int t
 
 extern "C" {
 
-const char* mpc_linkage_last_error(void) { return g_lerr.c_str(); }
+const char* mpc_linkage_last_error(void) { return g_lerr.msg.c_str(); }
 
 int mpc_linkage_pairs_host(const uint8_t* alleles, int64_t n_records, int32_t n_sites, uint32_t* pair, int threads) {
-  if (n_records < 0 || n_records > INT32_MAX) return lfail("mpc_linkage_pairs_host: n_records outside [0, 2^31)");
+  if (n_records < 0 || n_records > INT32_MAX) return g_lerr.fail("mpc_linkage_pairs_host: n_records outside [0, 2^31)");
   if (n_sites < 1 || n_sites > MPC_LNK_MAX_SITES)
-    return lfail("mpc_linkage_pairs_host: n_sites outside [1, " + std::to_string(MPC_LNK_MAX_SITES) + "]");
-  if (!pair || (n_records > 0 && !alleles)) return lfail("mpc_linkage_pairs_host: null pointer");
+    return g_lerr.fail("mpc_linkage_pairs_host: n_sites outside [1, " + std::to_string(MPC_LNK_MAX_SITES) + "]");
+  if (!pair || (n_records > 0 && !alleles)) return g_lerr.fail("mpc_linkage_pairs_host: null pointer");
   count_pairs(alleles, n_records, n_sites, pair, threads);
   return kOk;
 }
@@ -117,17 +114,17 @@ int mpc_linkage_host(const uint8_t* cs, const int64_t* cs_off, const int64_t* ts
                      const int64_t* site_key, int32_t n_sites, uint8_t* alleles, uint32_t* pair, int32_t* status,
                      int threads) {
   const std::string fn = "mpc_linkage_host: ";
-  if (n_records < 0 || n_records > INT32_MAX) return lfail(fn + "n_records outside [0, 2^31)");
-  if (n_samples < 1) return lfail(fn + "n_samples < 1");
+  if (n_records < 0 || n_records > INT32_MAX) return g_lerr.fail(fn + "n_records outside [0, 2^31)");
+  if (n_samples < 1) return g_lerr.fail(fn + "n_samples < 1");
   if (n_sites < 1 || n_sites > MPC_LNK_MAX_SITES)
-    return lfail(fn + "n_sites outside [1, " + std::to_string(MPC_LNK_MAX_SITES) + "]");
+    return g_lerr.fail(fn + "n_sites outside [1, " + std::to_string(MPC_LNK_MAX_SITES) + "]");
   if (!pos_off || !site_off || !site_key || !pair || !status || !cs_off ||
       (n_records > 0 && (!cs || !tstart || !rec_sample || !alleles)))
-    return lfail(fn + "null pointer");
+    return g_lerr.fail(fn + "null pointer");
   const size_t S = (size_t)n_samples;
   const int64_t K = n_sites;
   const std::string bad = mpc_host::check_sites(pos_off, site_off, site_key, S, K);
-  if (!bad.empty()) return lfail(fn + bad);
+  if (!bad.empty()) return g_lerr.fail(fn + bad);
   status[0] = status[1] = 0;
   if (n_records > 0) std::memset(alleles, 0, (size_t)n_records * (size_t)K);
 

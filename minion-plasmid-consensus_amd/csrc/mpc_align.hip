@@ -26,9 +26,7 @@
 #include "mpc_align.h"
 #include "mpc_bandtrace.h"
 #include "mpc_device.h"
-
-// mpc_plan.cpp: sets the message mpc_last_error() returns
-__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
+#include "mpc_launch.h"
 
 namespace {
 using namespace mpc;
@@ -207,9 +205,8 @@ __global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, 
   }
 }
 
-int hip_fail(const char* what, hipError_t e) {
-  return mpc_fail_(MPC_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
+using mpc_launch::hip_fail;
+using mpc_launch::read_back;
 
 }  // namespace
 
@@ -218,16 +215,14 @@ extern "C" int mpc_align_revcomp(uint8_t* d_seq, int64_t seq_bytes, const int64_
   if (n_reads == 0) return MPC_OK;
   if (!d_seq || !d_tab || seq_bytes < 0) return mpc_fail_(MPC_E_ARG, "mpc_align_revcomp: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int64_t> h((size_t)n_reads * 3);
-  hipError_t e = hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail("mpc_align_revcomp: read table", e);
+  std::vector<int64_t> h;
+  if (const int rc = read_back<int64_t>(st, {{d_tab, (size_t)n_reads * 3}}, h, "mpc_align_revcomp", "read table")) return rc;
   for (int32_t r = 0; r < n_reads; ++r)
     if (const int bad = check_revcomp(&h[(size_t)r * 3], seq_bytes))
       return mpc_fail_(MPC_E_ARG, ("mpc_align_revcomp: read " + std::to_string(r) + ": " + fault_text(bad)).c_str());
   hipLaunchKernelGGL(K_arevcomp, dim3((unsigned)n_reads), dim3(256), 0, st, d_seq, seq_bytes, d_tab);
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("K_arevcomp", e);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("mpc_align_revcomp", "K_arevcomp", e);
   return MPC_OK;
 }
 
@@ -239,10 +234,9 @@ extern "C" int mpc_align_trace(const uint8_t* d_seq, int64_t seq_bytes, const in
   if (!d_seq || !d_jobs || !d_flags || !d_out || !d_runs || seq_bytes < 0 || flags_bytes < 0 || runs_cap < 0)
     return mpc_fail_(MPC_E_ARG, "mpc_align_trace: null pointer or negative size");
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int64_t> h((size_t)n_jobs * 8);
-  hipError_t e = hipMemcpyAsync(h.data(), d_jobs, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail("mpc_align_trace: job table", e);
+  const char* fn = "mpc_align_trace";
+  std::vector<int64_t> h;
+  if (const int rc = read_back<int64_t>(st, {{d_jobs, (size_t)n_jobs * 8}}, h, fn, "job table")) return rc;
   int64_t flag_next = 0, d_max = 0;
   for (int32_t r = 0; r < n_jobs; ++r) {
     const int64_t* j = &h[(size_t)r * 8];
@@ -256,12 +250,10 @@ extern "C" int mpc_align_trace(const uint8_t* d_seq, int64_t seq_bytes, const in
   const size_t lds_bytes = (size_t)kTile * 64 + (size_t)row_cap * sizeof(int32_t) + (size_t)row_cap + 64;
   hipLaunchKernelGGL(K_atrace, dim3((unsigned)n_jobs), dim3(64), lds_bytes, st, d_seq, seq_bytes, d_jobs, d_flags,
                      flags_bytes, d_out, d_runs, runs_cap, row_cap);
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("K_atrace", e);
-  std::vector<int32_t> ho((size_t)n_jobs * 8);
-  e = hipMemcpyAsync(ho.data(), d_out, ho.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail("K_atrace", e);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(fn, "K_atrace", e);
+  std::vector<int32_t> ho;
+  if (const int rc = read_back<int32_t>(st, {{d_out, (size_t)n_jobs * 8}}, ho, fn, "K_atrace")) return rc;
   for (int32_t r = 0; r < n_jobs; ++r)
     if (ho[(size_t)r * 8] != MPC_ALIGN_OK)
       return mpc_fail_(MPC_ALIGN_E_SCAN, ("mpc_align_trace: read " + std::to_string(r) + ": status " +

@@ -30,9 +30,7 @@
 #include "mpc_cstables.h"
 #include "mpc_cswalk.h"
 #include "mpc_device.h"
-
-// mpc_plan.cpp: sets the message mpc_last_error() returns
-__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
+#include "mpc_launch.h"
 
 namespace {
 using namespace mpc;
@@ -100,12 +98,6 @@ struct CovFx {
     if (del_piece) out.add(reach, 1, ~0u);
   }
 };
-
-__device__ __forceinline__ void cov_report(uint64_t* stats, i64 r, int code) {
-  // the smallest record wins, malformed before out of range: the largest inverted key
-  const u64 key = ~((u64)r * 2 + (code == MPC_COV_RANGE ? 1 : 0));
-  __hip_atomic_fetch_max((u64*)&stats[kErrSlot], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // grid: workgroups over contiguous cuts of per_wg records; wave w of a workgroup takes every 16th.
 // A wave reads the tables of its next 64 records lane-parallel (lane j: record j of them), then
@@ -176,7 +168,7 @@ __global__ __launch_bounds__(kCovThreads) void K_covparse(
         cs_load_tile(nb, q, len, 0);
       }
       if (s < 0) {
-        if (ln == 0) cov_report(stats, r, MPC_COV_RANGE);
+        if (ln == 0) cs_report((u64*)&stats[kErrSlot], r, MPC_COV_RANGE);
         continue;
       }
       const uint32_t L = (uint32_t)(nrows - 1);
@@ -193,7 +185,7 @@ __global__ __launch_bounds__(kCovThreads) void K_covparse(
         }
       }
       if (w.bad || w.oor) {
-        if (ln == 0) cov_report(stats, r, w.bad ? MPC_COV_MALFORMED : MPC_COV_RANGE);
+        if (ln == 0) cs_report((u64*)&stats[kErrSlot], r, w.bad ? MPC_COV_MALFORMED : MPC_COV_RANGE);
         continue;
       }
       if (ln == 0 && w.p > ts) {  // the span: aligned + deleted
@@ -305,17 +297,11 @@ __global__ __launch_bounds__(kCovThreads) void K_covfinish(
     if (s == 0) {
       const u64 key = st[kErrSlot];
       if (key) {
-        const u64 v = ~key;
-        status[0] = (v & 1) ? MPC_COV_RANGE : MPC_COV_MALFORMED;
-        status[1] = (int32_t)(v >> 1);
+        cs_status(key, status);
         st[kErrSlot] = 0;
       }
     }
   }
-}
-
-int hip_fail(const char* what, hipError_t e) {
-  return mpc_fail_(MPC_E_HIP, (std::string("mpc_coverage_run: ") + what + ": " + hipGetErrorString(e)).c_str());
 }
 
 }  // namespace
@@ -326,6 +312,8 @@ extern "C" int mpc_coverage_run(const uint8_t* d_cs, const int64_t* d_cs_off, co
                                 const int32_t* d_rec_sample, int64_t n_records, const int64_t* d_pos_off,
                                 const int64_t* d_region, int32_t n_samples, uint32_t min_depth, uint32_t* d_rows,
                                 uint64_t* d_stats, int32_t* d_status, void* stream) {
+  using namespace mpc_launch;
+  const char* fn = "mpc_coverage_run";
   if (n_records < 0 || n_records > INT32_MAX) return mpc_fail_(MPC_E_ARG, "mpc_coverage_run: n_records outside [0, 2^31)");
   if (n_samples < 1) return mpc_fail_(MPC_E_ARG, "mpc_coverage_run: n_samples < 1");
   if (!d_pos_off || !d_region || !d_rows || !d_stats || !d_status || !d_cs_off ||
@@ -334,31 +322,25 @@ extern "C" int mpc_coverage_run(const uint8_t* d_cs, const int64_t* d_cs_off, co
   if (((uintptr_t)d_stats & 7) != 0) return mpc_fail_(MPC_E_ARG, "mpc_coverage_run: d_stats is not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const size_t S = (size_t)n_samples;
-  std::vector<int64_t> h(3 * S + 1);
-  hipError_t e = hipMemcpyAsync(h.data(), d_pos_off, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h.data() + S + 1, d_region, 2 * S * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return hip_fail("sample tables", e);
+  std::vector<int64_t> h;
+  if (const int rc = read_back<int64_t>(st, {{d_pos_off, S + 1}, {d_region, 2 * S}}, h, fn, "sample tables")) return rc;
   const std::string bad = mpc_host::check_samples(h.data(), h.data() + S + 1, S);
   if (!bad.empty()) return mpc_fail_(MPC_E_ARG, ("mpc_coverage_run: " + bad).c_str());
   const int64_t n_pos = h[S];
-  e = hipMemsetAsync(d_rows, 0, (size_t)n_pos * 4 * sizeof(uint32_t), st);
+  hipError_t e = hipMemsetAsync(d_rows, 0, (size_t)n_pos * 4 * sizeof(uint32_t), st);
   if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, S * MPC_COV_STATS * sizeof(uint64_t), st);
   if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, 2 * sizeof(int32_t), st);
-  if (e != hipSuccess) return hip_fail("clearing the outputs", e);
+  if (e != hipSuccess) return hip_fail(fn, "clearing the outputs", e);
   if (n_records > 0) {
-    int64_t wgs = (n_records + kCovWaves - 1) / kCovWaves;
-    if (wgs > kCovMaxWgs) wgs = kCovMaxWgs;
-    const int64_t per_wg = (n_records + wgs - 1) / wgs;
-    wgs = (n_records + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(K_covparse, dim3((unsigned)wgs), dim3(kCovThreads), 0, st, d_cs, d_cs_off, d_tstart, d_rec_sample,
-                       (i64)n_records, (i64)per_wg, d_pos_off, n_samples, d_rows, d_stats);
+    const RecordGrid g = record_grid(n_records, kCovWaves, kCovMaxWgs);
+    hipLaunchKernelGGL(K_covparse, dim3((unsigned)g.wgs), dim3(kCovThreads), 0, st, d_cs, d_cs_off, d_tstart, d_rec_sample,
+                       (i64)n_records, (i64)g.per_wg, d_pos_off, n_samples, d_rows, d_stats);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail("K_covparse", e);
+    if (e != hipSuccess) return hip_fail(fn, "K_covparse", e);
   }
   hipLaunchKernelGGL(K_covfinish, dim3((unsigned)n_samples), dim3(kCovThreads), 0, st, d_rows, d_pos_off, d_region,
                      min_depth, d_stats, d_status);
   e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("K_covfinish", e);
+  if (e != hipSuccess) return hip_fail(fn, "K_covfinish", e);
   return MPC_OK;
 }

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mpc_coverage.h"
 #include "mpc_device.h"
 
 namespace mpc {
@@ -163,6 +164,21 @@ __device__ __forceinline__ void cs_load_tile(uint32_t (&bt)[kCsK], const uint8_t
     const int i = t0 + k * 64 + lane();
     bt[k] = i < len ? (uint32_t)__builtin_nontemporal_load(q + i) : 0u;
   }
+}
+
+// The status key both walks keep between their two kernels: record r failed with
+// `code`.  The smallest record wins, malformed before out of range: the largest
+// inverted key.
+__device__ __forceinline__ void cs_report(cs_u64* key_slot, cs_i64 r, int code) {
+  const cs_u64 key = ~((cs_u64)r * 2 + (code == MPC_COV_RANGE ? 1 : 0));
+  __hip_atomic_fetch_max(key_slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ... and the decoding of a key that is not 0 (0: no record failed) into status = {code, record}
+__device__ __forceinline__ void cs_status(cs_u64 key, int32_t* __restrict__ status) {
+  const cs_u64 v = ~key;
+  status[0] = (v & 1) ? MPC_COV_RANGE : MPC_COV_MALFORMED;
+  status[1] = (int32_t)(v >> 1);
 }
 
 }  // namespace mpc

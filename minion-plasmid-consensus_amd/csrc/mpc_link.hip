@@ -19,10 +19,8 @@
 #include "mpc_cstables.h"
 #include "mpc_cswalk.h"
 #include "mpc_device.h"
+#include "mpc_launch.h"
 #include "mpc_linkage.h"
-
-// mpc_plan.cpp: sets the message mpc_last_error() returns
-__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
 
 namespace {
 using namespace mpc;
@@ -96,12 +94,6 @@ struct LnkFx {
   }
 };
 
-__device__ __forceinline__ void lnk_report(u64* key_slot, i64 r, int code) {
-  // the smallest record wins, malformed before out of range: the largest inverted key
-  const u64 key = ~((u64)r * 2 + (code == MPC_COV_RANGE ? 1 : 0));
-  __hip_atomic_fetch_max(key_slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // grid: workgroups over contiguous cuts of per_wg records; wave w of a workgroup takes every 16th
 // (K_covparse's batching: a wave reads the tables of its next 64 records lane-parallel, then walks them).
 __global__ __launch_bounds__(kLnkThreads) void K_lnkparse(
@@ -164,7 +156,7 @@ __global__ __launch_bounds__(kLnkThreads) void K_lnkparse(
       }
       uint8_t* arow = alleles + r * K;
       if (s < 0) {
-        if (ln == 0) lnk_report(err_key, r, MPC_COV_RANGE);
+        if (ln == 0) cs_report(err_key, r, MPC_COV_RANGE);
         for (int i = ln; i < K; i += 64) arow[i] = 0;
         continue;
       }
@@ -179,7 +171,7 @@ __global__ __launch_bounds__(kLnkThreads) void K_lnkparse(
           if (cb < clen && !w.bad) cs_chunk(bt[k], clen - cb < 64 ? clen - cb : 64, cb + 64 >= clen, L, lemask, fx, w);
         }
       }
-      if ((w.bad || w.oor) && ln == 0) lnk_report(err_key, r, w.bad ? MPC_COV_MALFORMED : MPC_COV_RANGE);
+      if ((w.bad || w.oor) && ln == 0) cs_report(err_key, r, w.bad ? MPC_COV_MALFORMED : MPC_COV_RANGE);
       // the row: covered ? max(code, 1) : 0, consecutive lanes on consecutive bytes; cleared for the next record
       wave_lds_sync();
       const i64 e = w.p;
@@ -212,11 +204,7 @@ __global__ __launch_bounds__(64 * kPlaneWaves) void K_lnkplanes(
   const int tid = (int)threadIdx.x, ln = lane(), wave = tid >> 6;
   if (blockIdx.x == 0 && tid == 0 && status) {
     const u64 key = *err_key;
-    if (key) {
-      const u64 v = ~key;
-      status[0] = (v & 1) ? MPC_COV_RANGE : MPC_COV_MALFORMED;
-      status[1] = (int32_t)(v >> 1);
-    }
+    if (key) cs_status(key, status);
   }
   const i64 W = (N + 63) / 64;
   const i64 wd = (i64)blockIdx.x * kPlaneWaves + wave;
@@ -284,15 +272,13 @@ __global__ __launch_bounds__(64 * kPairWaves) void K_lnkpair(const u64* __restri
 int lnk_fail(const char* fn, const std::string& what) {
   return mpc_fail_(MPC_E_ARG, (std::string(fn) + ": " + what).c_str());
 }
-int lnk_hip_fail(const char* fn, const char* what, hipError_t e) {
-  return mpc_fail_(MPC_E_HIP, (std::string(fn) + ": " + what + ": " + hipGetErrorString(e)).c_str());
-}
+using mpc_launch::hip_fail;
 
 // K_lnkplanes + K_lnkpair (pair is cleared here); status / err_key as K_lnkplanes takes them
 int launch_pairs(const char* fn, const uint8_t* d_alleles, int64_t N, int32_t K, uint32_t* d_pair, void* d_scratch,
                  int32_t* d_status, hipStream_t st) {
   hipError_t e = hipMemsetAsync(d_pair, 0, (size_t)K * K * 64 * sizeof(uint32_t), st);
-  if (e != hipSuccess) return lnk_hip_fail(fn, "clearing pair", e);
+  if (e != hipSuccess) return hip_fail(fn, "clearing pair", e);
   u64* err_key = (u64*)d_scratch;
   u64* planes = (u64*)((char*)d_scratch + kPlaneHead);
   const int64_t W = (N + 63) / 64;
@@ -300,7 +286,7 @@ int launch_pairs(const char* fn, const uint8_t* d_alleles, int64_t N, int32_t K,
     hipLaunchKernelGGL(K_lnkplanes, dim3((unsigned)((W + kPlaneWaves - 1) / kPlaneWaves)), dim3(64 * kPlaneWaves), 0, st,
                        d_alleles, (i64)N, (int)K, planes, err_key, d_status);
     e = hipGetLastError();
-    if (e != hipSuccess) return lnk_hip_fail(fn, "K_lnkplanes", e);
+    if (e != hipSuccess) return hip_fail(fn, "K_lnkplanes", e);
     int64_t splits = (W + kPairWordsPerSplit - 1) / kPairWordsPerSplit;
     if (splits > kPairMaxSplits) splits = kPairMaxSplits;
     const int64_t per = (W + splits - 1) / splits;
@@ -309,7 +295,7 @@ int launch_pairs(const char* fn, const uint8_t* d_alleles, int64_t N, int32_t K,
     hipLaunchKernelGGL(K_lnkpair, dim3((unsigned)((n_pairs + kPairWaves - 1) / kPairWaves), (unsigned)splits),
                        dim3(64 * kPairWaves), 0, st, planes, (i64)W, (int)K, (i64)per, d_pair);
     e = hipGetLastError();
-    if (e != hipSuccess) return lnk_hip_fail(fn, "K_lnkpair", e);
+    if (e != hipSuccess) return hip_fail(fn, "K_lnkpair", e);
   }
   return MPC_OK;
 }
@@ -350,30 +336,22 @@ extern "C" int mpc_linkage_run(const uint8_t* d_cs, const int64_t* d_cs_off, con
   if (((uintptr_t)d_scratch & 7) != 0) return lnk_fail(fn, "d_scratch is not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const size_t S = (size_t)n_samples, K = (size_t)n_sites;
-  std::vector<int64_t> h(2 * (S + 1) + K);
-  int64_t* pos = h.data();
-  int64_t* off = pos + S + 1;
-  int64_t* key = off + S + 1;
-  hipError_t e = hipMemcpyAsync(pos, d_pos_off, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(off, d_site_off, (S + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(key, d_site_key, K * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return lnk_hip_fail(fn, "sample and site tables", e);
-  const std::string bad = mpc_host::check_sites(pos, off, key, S, (int64_t)K);
+  std::vector<int64_t> h;
+  if (const int rc = mpc_launch::read_back<int64_t>(st, {{d_pos_off, S + 1}, {d_site_off, S + 1}, {d_site_key, K}}, h, fn,
+                                                    "sample and site tables"))
+    return rc;
+  const std::string bad = mpc_host::check_sites(h.data(), h.data() + S + 1, h.data() + 2 * (S + 1), S, (int64_t)K);
   if (!bad.empty()) return lnk_fail(fn, bad);
-  e = hipMemsetAsync(d_scratch, 0, kPlaneHead, st);
+  hipError_t e = hipMemsetAsync(d_scratch, 0, kPlaneHead, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_status, 0, 2 * sizeof(int32_t), st);
-  if (e != hipSuccess) return lnk_hip_fail(fn, "clearing the status", e);
+  if (e != hipSuccess) return hip_fail(fn, "clearing the status", e);
   if (n_records > 0) {
-    int64_t wgs = (n_records + kLnkWaves - 1) / kLnkWaves;
-    if (wgs > kLnkMaxWgs) wgs = kLnkMaxWgs;
-    const int64_t per_wg = (n_records + wgs - 1) / wgs;
-    wgs = (n_records + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(K_lnkparse, dim3((unsigned)wgs), dim3(kLnkThreads), 0, st, d_cs, d_cs_off, d_tstart, d_rec_sample,
-                       (i64)n_records, (i64)per_wg, d_pos_off, n_samples, d_site_off, d_site_key, (int)n_sites, d_alleles,
+    const mpc_launch::RecordGrid g = mpc_launch::record_grid(n_records, kLnkWaves, kLnkMaxWgs);
+    hipLaunchKernelGGL(K_lnkparse, dim3((unsigned)g.wgs), dim3(kLnkThreads), 0, st, d_cs, d_cs_off, d_tstart, d_rec_sample,
+                       (i64)n_records, (i64)g.per_wg, d_pos_off, n_samples, d_site_off, d_site_key, (int)n_sites, d_alleles,
                        (u64*)d_scratch);
     e = hipGetLastError();
-    if (e != hipSuccess) return lnk_hip_fail(fn, "K_lnkparse", e);
+    if (e != hipSuccess) return hip_fail(fn, "K_lnkparse", e);
   }
   return launch_pairs(fn, d_alleles, n_records, n_sites, d_pair, d_scratch, d_status, st);
 }

@@ -19,10 +19,8 @@
 #include "mpc.h"
 #include "mpc_bandtrace.h"
 #include "mpc_device.h"
+#include "mpc_launch.h"
 #include "mpc_verify.h"
-
-// mpc_plan.cpp: sets the message mpc_last_error() returns
-__attribute__((visibility("hidden"))) int mpc_fail_(int code, const char* msg);
 
 namespace {
 using namespace mpc;
@@ -148,15 +146,14 @@ extern "C" int mpc_verify_scan(const uint8_t* d_seq, const int64_t* d_pairs, int
   if (n_pairs == 0) return MPC_OK;
   if (!d_seq || !d_pairs || !d_out) return mpc_fail_(MPC_E_ARG, "mpc_verify_scan: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int64_t> h((size_t)n_pairs * 4);
-  hipError_t e = hipMemcpyAsync(h.data(), d_pairs, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return mpc_fail_(MPC_E_HIP, (std::string("mpc_verify_scan: pair table: ") + hipGetErrorString(e)).c_str());
+  std::vector<int64_t> h;
+  if (const int rc = mpc_launch::read_back<int64_t>(st, {{d_pairs, (size_t)n_pairs * 4}}, h, "mpc_verify_scan", "pair table"))
+    return rc;
   for (int32_t p = 0; p < n_pairs; ++p)
     if (const int bad = check_pair(&h[(size_t)p * 4]))
       return mpc_fail_(MPC_E_ARG, ("mpc_verify_scan: pair " + std::to_string(p) + ": " + fault_text(bad)).c_str());
   hipLaunchKernelGGL(K_vscan, dim3((unsigned)n_pairs), dim3(64), 0, st, d_seq, d_pairs, d_out);
-  e = hipGetLastError();
-  if (e != hipSuccess) return mpc_fail_(MPC_E_HIP, (std::string("K_vscan: ") + hipGetErrorString(e)).c_str());
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return mpc_launch::hip_fail("mpc_verify_scan", "K_vscan", e);
   return MPC_OK;
 }

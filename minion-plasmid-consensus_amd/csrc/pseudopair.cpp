@@ -16,11 +16,8 @@
 // form only Python's int() accepts, bytes >= 0x80, '\r' (universal newlines)
 // -- are declined (status MPC_INGEST_FALLBACK): the caller uses the Python
 // restatement.
+#include "host_file.h"
 #include "host_threads.h"
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cstdint>
@@ -45,18 +42,13 @@ struct Rec {
   uint8_t state = 0;  // 0 ok, 1 error (fewer than 5 fields), 2 decline
 };
 
-// int() of a field that is a plain optionally-signed run of 1-18 digits; false: not restated here
+// Policy: int() of an optional '+' or '-' and 1-18 digits; false: declined (not restated here)
 bool plain_int(sv f, int64_t* out) {
-  size_t k = 0;
-  bool neg = false;
-  if (k < f.size() && (f[k] == '-' || f[k] == '+')) { neg = f[k] == '-'; ++k; }
-  if (k == f.size() || f.size() - k > 18) return false;
-  int64_t v = 0;
-  for (; k < f.size(); ++k) {
-    if (f[k] < '0' || f[k] > '9') return false;
-    v = v * 10 + (f[k] - '0');
-  }
-  *out = neg ? -v : v;
+  const bool sign = !f.empty() && (f[0] == '-' || f[0] == '+');
+  const sv d = f.substr(sign ? 1 : 0);
+  int64_t v;
+  if (d.empty() || d.size() > 18 || mpc_host::leading_digits(d, &v) != d.size()) return false;
+  *out = sign && f[0] == '-' ? -v : v;
   return true;
 }
 
@@ -94,22 +86,12 @@ int mpc_pseudopair(const char* paf_path, int64_t min_align_length, int has_min, 
     std::snprintf(st->message, sizeof st->message, "%s", m.c_str());
     return status;
   };
-  const int fd = ::open(paf_path, O_RDONLY);
-  if (fd < 0) return fail(MPC_INGEST_ERROR, std::string("cannot open ") + paf_path);
-  struct stat sb;
-  if (fstat(fd, &sb) != 0) { ::close(fd); return fail(MPC_INGEST_ERROR, "stat failed"); }
-  const size_t n = (size_t)sb.st_size;
-  const char* p = "";
-  void* m = nullptr;
-  if (n) {
-    m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) { ::close(fd); return fail(MPC_INGEST_ERROR, "mmap failed"); }
-    p = static_cast<const char*>(m);
-  }
-  struct Unmap {
-    void* m; size_t n; int fd;
-    ~Unmap() { if (m) munmap(m, n); ::close(fd); }
-  } unmap{m, n, fd};
+  mpc_host::Mapped file;
+  if (!file.open(paf_path))
+    return fail(MPC_INGEST_ERROR, file.failed == file.kOpen ? std::string("cannot open ") + paf_path
+                                  : file.failed == file.kStat ? "stat failed" : "mmap failed");
+  const size_t n = file.n;
+  const char* p = file.p;
   const sv text(p, n);
   // line starts
   std::vector<size_t> starts;

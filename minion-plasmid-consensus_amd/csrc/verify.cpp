@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "host_file.h"
 #include "host_threads.h"
 #include "mpc_bandtrace.h"
 #include "mpc_verify.h"
@@ -18,13 +19,9 @@
 namespace {
 using namespace mpc_band;
 
-constexpr int kOk = 0, kArg = -1;  // MPC_OK, MPC_E_ARG of mpc.h
+constexpr int kOk = 0;  // MPC_OK of mpc.h
 
-thread_local std::string g_verr;
-int vfail(const std::string& msg) {
-  g_verr = msg;
-  return kArg;
-}
+thread_local mpc_host::LastError g_verr;
 
 // one pair: column j of D over all rows, text column by text column
 void scan_pair(const uint8_t* q, int64_t m, const uint8_t* t, int64_t n, int32_t* out) {
@@ -65,16 +62,16 @@ void scan_pair(const uint8_t* q, int64_t m, const uint8_t* t, int64_t n, int32_t
 
 }  // namespace
 
-extern "C" const char* mpc_verify_last_error(void) { return g_verr.c_str(); }
+extern "C" const char* mpc_verify_last_error(void) { return g_verr.msg.c_str(); }
 
 extern "C" int mpc_verify_scan_host(const uint8_t* seq, const int64_t* pairs, int32_t n_pairs, int32_t* out,
                                     int threads) {
-  if (n_pairs < 0) return vfail("mpc_verify_scan_host: n_pairs < 0");
+  if (n_pairs < 0) return g_verr.fail("mpc_verify_scan_host: n_pairs < 0");
   if (n_pairs == 0) return kOk;
-  if (!seq || !pairs || !out) return vfail("mpc_verify_scan_host: null pointer");
+  if (!seq || !pairs || !out) return g_verr.fail("mpc_verify_scan_host: null pointer");
   for (int32_t p = 0; p < n_pairs; ++p)
     if (const int bad = check_pair(pairs + 4 * (int64_t)p))
-      return vfail("mpc_verify_scan_host: pair " + std::to_string(p) + ": " + fault_text(bad));
+      return g_verr.fail("mpc_verify_scan_host: pair " + std::to_string(p) + ": " + fault_text(bad));
   std::atomic<int32_t> next{0};
   mpc_host::parallel(mpc_host::clamp_threads(threads, n_pairs), [&](int) {
     for (int32_t p; (p = next.fetch_add(1)) < n_pairs;) {
@@ -87,12 +84,12 @@ extern "C" int mpc_verify_scan_host(const uint8_t* seq, const int64_t* pairs, in
 
 extern "C" int mpc_verify_script(const uint8_t* q, int64_t m, const uint8_t* t, int64_t n, int32_t distance,
                                  int32_t end, int32_t* start, int32_t counts[4], char* cigar, size_t cigar_cap) {
-  if (!start || !counts || !cigar || !q || (!t && n > 0)) return vfail("mpc_verify_script: null pointer");
-  if (const int bad = check_lengths(m, n)) return vfail(std::string("mpc_verify_script: ") + fault_text(bad));
+  if (!start || !counts || !cigar || !q || (!t && n > 0)) return g_verr.fail("mpc_verify_script: null pointer");
+  if (const int bad = check_lengths(m, n)) return g_verr.fail(std::string("mpc_verify_script: ") + fault_text(bad));
   if (distance < 0 || distance > m || end < 0 || end > n)
-    return vfail("mpc_verify_script: (distance, end) outside the matrix");
+    return g_verr.fail("mpc_verify_script: (distance, end) outside the matrix");
   if (distance > MPC_VERIFY_MAX_EDITS) {
-    if (cigar_cap < 2) return vfail("mpc_verify_script: cigar buffer too small");
+    if (cigar_cap < 2) return g_verr.fail("mpc_verify_script: cigar buffer too small");
     *start = -1;
     for (int k = 0; k < 4; ++k) counts[k] = -1;
     std::strcpy(cigar, "*");
@@ -106,15 +103,15 @@ extern "C" int mpc_verify_script(const uint8_t* q, int64_t m, const uint8_t* t, 
     runs.resize(2 * (size_t)distance + 1);
     band_trace(q, m, t, n, distance, end, o, runs.data(), band);
   } catch (const std::bad_alloc&) {
-    return vfail("mpc_verify_script: out of memory for the band");
+    return g_verr.fail("mpc_verify_script: out of memory for the band");
   }
-  if (o[0] != MPC_ALIGN_OK) return vfail("mpc_verify_script: the band does not give the scan's distance at (m, end)");
+  if (o[0] != MPC_ALIGN_OK) return g_verr.fail("mpc_verify_script: the band does not give the scan's distance at (m, end)");
   std::string cg;
   for (int32_t k = o[6]; k-- > 0;) {
     cg += std::to_string(run_len(runs[(size_t)k]));
     cg += "=XID"[run_op(runs[(size_t)k])];
   }
-  if (cg.size() + 1 > cigar_cap) return vfail("mpc_verify_script: cigar buffer too small");
+  if (cg.size() + 1 > cigar_cap) return g_verr.fail("mpc_verify_script: cigar buffer too small");
   std::memcpy(cigar, cg.c_str(), cg.size() + 1);
   *start = o[1];
   for (int k = 0; k < 4; ++k) counts[k] = o[2 + k];

@@ -11,7 +11,7 @@ import warnings
 
 import numpy as np
 
-from . import _build
+from . import _build, _native
 
 LIB_PATH = _build.LIBMPC
 
@@ -184,35 +184,14 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise MpcError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() (no CPU fallback)")
         _preload_hip_runtime()
-        L = ctypes.CDLL(LIB_PATH)
-        rt = _hip_runtime_paths()
-        if len(rt) > 1:
-            raise MpcError("two HIP runtimes are mapped into this process (%s): load libmpc.so through "
-                           "engine.lib() before anything else loads a HIP runtime" % ", ".join(sorted(rt)))
-        vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
-        L.mpc_version.restype = i32
-        L.mpc_last_error.restype = ctypes.c_char_p
-        L.mpc_plan_create.argtypes = [ctypes.POINTER(_Input), i64, ctypes.POINTER(vp)]
-        L.mpc_plan_destroy.argtypes = [vp]
-        L.mpc_plan_workspace_bytes.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
-        L.mpc_plan_bind.argtypes = [vp, vp, ctypes.c_size_t]
-        L.mpc_plan_buffer.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(i64)]
-        L.mpc_plan_set_input.argtypes = [vp, ctypes.POINTER(_Input)]
-        L.mpc_plan_get_info.argtypes = [vp, ctypes.POINTER(PlanInfo)]
-        L.mpc_input_layout.argtypes = [ctypes.POINTER(ctypes.c_size_t), i32]
-        L.mpc_input_layout.restype = ctypes.c_size_t
-        for f in PHASES:
-            getattr(L, "mpc_" + f).argtypes = [vp, vp]
-        L.mpc_consensus.argtypes = [vp, dbl, dbl, vp]
-        L.mpc_run.argtypes = [vp, dbl, dbl, vp]
-        L.mpc_profile_kernel.argtypes = [vp, i32, vp]
-        L.mpc_profile_kernel.restype = i32
-        for f in ("mpc_plan_create", "mpc_plan_destroy", "mpc_plan_workspace_bytes", "mpc_plan_bind",
-                  "mpc_plan_buffer", "mpc_plan_set_input", "mpc_plan_get_info", "mpc_consensus", "mpc_run") + tuple("mpc_" + x for x in PHASES):
-            getattr(L, f).restype = i32
-        if L.mpc_version() != ABI_VERSION:
-            raise MpcError(f"{LIB_PATH}: ABI {L.mpc_version()} != {ABI_VERSION} (rebuild)")
-        _lib = L
+        def check(L):
+            rt = _hip_runtime_paths()
+            if len(rt) > 1:
+                raise MpcError("two HIP runtimes are mapped into this process (%s): load libmpc.so through "
+                               "engine.lib() before anything else loads a HIP runtime" % ", ".join(sorted(rt)))
+            if L.mpc_version() != ABI_VERSION:
+                raise MpcError(f"{LIB_PATH}: ABI {L.mpc_version()} != {ABI_VERSION} (rebuild)")
+        _lib = _native.load(LIB_PATH, _native.device_prototypes, check)
     return _lib
 
 
@@ -267,7 +246,6 @@ def parse_split(ref_lens, reads_per_sample, cs_off):
                  n_reads=n, cs_bytes=int(off[-1]), cs_base=0, read_offset=0, n_reads_global=n, shard=0, n_shards=1,
                  h_cs_off=off.ctypes.data_as(p64))
     L = lib()
-    L.mpc_plan_parse_tables.argtypes = [ctypes.c_void_p] * 3
     h = ctypes.c_void_p()
     _check(L.mpc_plan_create(ctypes.byref(inp), int((4 * ref_len + 8).sum() + 1024), ctypes.byref(h)))
     try:

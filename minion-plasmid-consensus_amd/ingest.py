@@ -213,7 +213,7 @@ _ingest_lib = None
 def _native():
     global _ingest_lib
     if _ingest_lib is None:
-        from . import _build
+        from . import _build, _native as glue
         path = _build.LIBINGEST
         try:
             _build.build_ingest()  # no-op unless missing or older than its sources
@@ -221,24 +221,11 @@ def _native():
             if not os.path.exists(path):
                 _ingest_lib = False
                 return None
-        L = ctypes.CDLL(path)
-        L.mpc_ingest_version.restype = ctypes.c_int
-        if L.mpc_ingest_version() != INGEST_ABI:
-            raise IngestError(f"{path}: ABI {L.mpc_ingest_version()} != {INGEST_ABI} (stale build: "
-                              "rebuild with __graft_entry__.build())")
-        L.mpc_ingest.restype = ctypes.c_int
-        L.mpc_ingest.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
-                                 ctypes.POINTER(_IngestOut)]
-        L.mpc_ingest_multi.restype = ctypes.c_int
-        L.mpc_ingest_multi.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p),
-                                       ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(_IngestOut)]
-        L.mpc_ingest_free.argtypes = [ctypes.POINTER(_IngestOut)]
-        L.mpc_write_calls.restype = ctypes.c_int
-        L.mpc_write_calls.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_char_p,
-                                      ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        L.mpc_py_float_repr.restype = ctypes.c_int
-        L.mpc_py_float_repr.argtypes = [ctypes.c_double, ctypes.c_char_p, ctypes.c_int]
-        _ingest_lib = L
+        def check(L):
+            if L.mpc_ingest_version() != INGEST_ABI:
+                raise IngestError(f"{path}: ABI {L.mpc_ingest_version()} != {INGEST_ABI} (stale build: "
+                                  "rebuild with __graft_entry__.build())")
+        _ingest_lib = glue.load(path, glue.host_prototypes, check)
     return _ingest_lib or None
 
 

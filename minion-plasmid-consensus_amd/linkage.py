@@ -18,11 +18,9 @@ definition; DESIGN.md "linkage_qc").
 The defaults (minor fraction 0.05, minor count 10, r^2 0.1, joint count 10)
 are starting values nobody has validated on real runs.
 """
-import ctypes
-
 import numpy as np
 
-from . import coverage
+from . import _native, coverage, engine
 
 MAX_SITES = 128  # mpc_linkage.h MPC_LNK_MAX_SITES
 CODES = 8
@@ -47,59 +45,23 @@ def site_label(key):
     return "{}:{}".format(key // 2 + 1, "base" if key & 1 else "gap")
 
 
-def host_lib():
-    L = coverage.host_lib()
-    if not hasattr(L, "_linkage_ready"):
-        vp = ctypes.c_void_p
-        L.mpc_linkage_host.restype = ctypes.c_int
-        L.mpc_linkage_host.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp,
-                                       vp, ctypes.c_int]
-        L.mpc_linkage_pairs_host.restype = ctypes.c_int
-        L.mpc_linkage_pairs_host.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int]
-        L.mpc_linkage_last_error.restype = ctypes.c_char_p
-        L._linkage_ready = True
-    return L
-
-
-def _device_lib():
-    from . import engine
-    L = engine.lib()  # (before torch: one HIP runtime in the process)
-    if not hasattr(L, "_linkage_ready"):
-        vp = ctypes.c_void_p
-        L.mpc_linkage_run.restype = ctypes.c_int
-        L.mpc_linkage_run.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp,
-                                      vp, vp, vp]
-        L.mpc_linkage_pairs.restype = ctypes.c_int
-        L.mpc_linkage_pairs.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, vp]
-        L.mpc_linkage_tile_bytes.restype = ctypes.c_int
-        L.mpc_linkage_scratch_bytes.restype = ctypes.c_int64
-        L.mpc_linkage_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]
-        L._linkage_ready = True
-    return L
+host_lib = coverage.host_lib
+_device_lib = engine.lib
 
 
 def tile_bytes():
     """cs bytes K_lnkparse takes per tile (no GPU needed)."""
-    return _device_lib().mpc_linkage_tile_bytes()
+    return engine.lib().mpc_linkage_tile_bytes()
 
 
 def scratch_bytes(n_records, n_sites):
-    return _device_lib().mpc_linkage_scratch_bytes(n_records, n_sites)
+    return engine.lib().mpc_linkage_scratch_bytes(n_records, n_sites)
 
 
 def _device_check(L, rc):
-    from . import engine
     if rc == -1:  # MPC_E_ARG: the tables were refused before any launch
         raise LinkageError(L.mpc_last_error().decode(errors="replace"))
     engine._check(rc)
-
-
-def _torch_device(device):
-    from . import engine
-    import torch
-    if not torch.cuda.is_available():
-        raise engine.MpcError("no HIP device visible (use device='cpu' for the host walk)")
-    return torch, torch.device("cuda", int(device))
 
 
 def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, threads=0):
@@ -124,8 +86,8 @@ def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, t
                               pair.ctypes.data, status.ctypes.data, threads) != 0:
             raise LinkageError(L.mpc_linkage_last_error().decode(errors="replace"))
     else:
-        L = _device_lib()
-        torch, dev = _torch_device(device)
+        L = engine.lib()
+        torch, dev = _native.device(device)
         with torch.cuda.device(dev):
             # the int64 tables first, then rec_sample, then the cs bytes
             at, d_blob = coverage.upload(torch, dev, [cs_off, tstart, pos_off, site_off, site_key, rec_sample, cs])
@@ -133,10 +95,9 @@ def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, t
             d_pair = torch.empty((K, K, CODES, CODES), dtype=torch.int32, device=dev)
             d_scratch = torch.empty(max(8, L.mpc_linkage_scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev)
             _device_check(L, L.mpc_linkage_run(at[6], at[0], at[1], at[5], n, at[2], S, at[3], at[4], K,
                                                d_alleles.data_ptr(), d_pair.data_ptr(), d_scratch.data_ptr(),
-                                               d_status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+                                               d_status.data_ptr(), _native.stream_ptr(torch, dev)))
             status = d_status.cpu().numpy()
             alleles = d_alleles.cpu().numpy()
             pair = d_pair.cpu().numpy().view(np.uint32)
@@ -159,17 +120,16 @@ def pairs(alleles, device=0, threads=0):
         if L.mpc_linkage_pairs_host(alleles.ctypes.data, n, K, pair.ctypes.data, threads) != 0:
             raise LinkageError(L.mpc_linkage_last_error().decode(errors="replace"))
         return pair
-    L = _device_lib()
-    torch, dev = _torch_device(device)
+    L = engine.lib()
+    torch, dev = _native.device(device)
     with torch.cuda.device(dev):
         d_alleles = torch.empty((max(n, 1), K), dtype=torch.uint8, device=dev)
         if n:
             d_alleles[:n].copy_(torch.from_numpy(alleles))
         d_pair = torch.empty((K, K, CODES, CODES), dtype=torch.int32, device=dev)
         d_scratch = torch.empty(max(8, L.mpc_linkage_scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev)
         _device_check(L, L.mpc_linkage_pairs(d_alleles.data_ptr(), n, K, d_pair.data_ptr(), d_scratch.data_ptr(),
-                                             ctypes.c_void_p(stream.cuda_stream)))
+                                             _native.stream_ptr(torch, dev)))
         return d_pair.cpu().numpy().view(np.uint32)
 
 

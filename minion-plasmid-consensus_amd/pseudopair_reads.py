@@ -74,23 +74,11 @@ class _Stats(ctypes.Structure):
                 ("message", ctypes.c_char * 256)]
 
 
-def _lib():
-    from . import ingest
-    L = ingest._native()
-    if L is None:
-        return None
-    if not hasattr(L, "_pp_ready"):
-        L.mpc_pseudopair.restype = ctypes.c_int
-        L.mpc_pseudopair.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
-                                     ctypes.POINTER(_Stats)]
-        L._pp_ready = True
-    return L
-
-
 def pseudopair_native(paf_path, min_align_length, out_path, n_threads=0):
     """The whole tool through libmpc_ingest.so: writes out_path and returns the
     stats, None when the native parser declines the input, or raises PairError."""
-    L = _lib()
+    from . import ingest
+    L = ingest._native()
     if L is None:
         return None
     st = _Stats()

@@ -20,6 +20,8 @@ import statistics
 
 import numpy as np
 
+from . import _native
+
 MAX_QUERY = 65536   # mpc_verify.h MPC_VERIFY_MAX_QUERY
 MAX_EDITS = 1024    # mpc_verify.h MPC_VERIFY_MAX_EDITS
 MIN_MEDIAN_ACCURACY = 99.9
@@ -55,21 +57,8 @@ def read_consensus(path):
 
 
 def host_lib():
-    """libmpc_ingest.so with the verify entry points bound."""
-    from . import ingest
-    L = ingest._native()
-    if L is None:
-        raise VerifyError("libmpc_ingest.so is missing and cannot be built (no host compiler)")
-    if not hasattr(L, "_verify_ready"):
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        L.mpc_verify_scan_host.restype = ctypes.c_int
-        L.mpc_verify_scan_host.argtypes = [vp, vp, i32, vp, ctypes.c_int]
-        L.mpc_verify_script.restype = ctypes.c_int
-        L.mpc_verify_script.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int64, i32, i32,
-                                        ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.c_char_p, ctypes.c_size_t]
-        L.mpc_verify_last_error.restype = ctypes.c_char_p
-        L._verify_ready = True
-    return L
+    """libmpc_ingest.so (its prototypes: _native.host_prototypes)."""
+    return _native.host(VerifyError)
 
 
 def _check_lengths(pairs):
@@ -98,26 +87,9 @@ def _pack(pairs):
 
 
 def device_lib():
-    """libmpc.so with mpc_verify_scan bound."""
+    """libmpc.so (its prototypes: _native.device_prototypes)."""
     from . import engine
-    L = engine.lib()
-    if not hasattr(L, "_verify_ready"):
-        vp = ctypes.c_void_p
-        L.mpc_verify_scan.restype = ctypes.c_int
-        L.mpc_verify_scan.argtypes = [vp, vp, ctypes.c_int32, vp, vp]
-        L._verify_ready = True
-    return L
-
-
-def _device(device):
-    """(torch, torch.device) of a GPU; libmpc.so is loaded before torch is
-    imported: one HIP runtime in the process."""
-    from . import engine
-    device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        raise engine.MpcError("no HIP device visible (use device='cpu' for the host path)")
-    return torch, torch.device("cuda", int(device))
+    return engine.lib()
 
 
 def _to_device(torch, dev, a):
@@ -145,7 +117,7 @@ def scan_table(seq, tab, device, threads=0, d_seq=None):
             raise VerifyError(L.mpc_verify_last_error().decode(errors="replace"))
         return out
     from . import engine
-    torch, dev = _device(device)
+    torch, dev = _native.device(device, "host path")
     L = device_lib()
     with torch.cuda.device(dev):
         if d_seq is None:
@@ -153,7 +125,7 @@ def scan_table(seq, tab, device, threads=0, d_seq=None):
         d_tab = _to_device(torch, dev, tab)
         d_out = torch.empty(2 * n, dtype=torch.int32, device=dev)
         engine._check(L.mpc_verify_scan(d_seq.data_ptr(), d_tab.data_ptr(), n, d_out.data_ptr(),
-                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                        _native.stream_ptr(torch, dev)))
         return d_out.cpu().numpy().reshape(n, 2)
 
 

@@ -273,3 +273,97 @@ def test_elf_dynamic_reads_ranges(tmp_path):
     cut = tmp_path / "cut.so"
     cut.write_bytes(open(e.LIB_PATH, "rb").read(200))
     assert e._elf_dynamic(str(cut)) == (None, [])
+
+
+# ---- the binding tables of _native.py against the public headers ------------------
+
+_KIND_OF_C = {"int": "i32", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "size_t": "size", "double": "double",
+              "void": "void"}
+
+
+def _c_kind(decl):
+    """Kind of a C return type or parameter: a '*' or a '[n]' anywhere makes it a pointer."""
+    if "*" in decl or "[" in decl:
+        return "ptr"
+    words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+    return _KIND_OF_C[words[0]]  # (the parameter's name, if any, follows the type)
+
+
+def header_prototypes():
+    """{function: (return kind, [parameter kinds])} of every prototype in include/*.h:
+    comments and preprocessor lines stripped, prototypes may span lines."""
+    out = {}
+    inc = os.path.join(REPO, "include")
+    for h in sorted(os.listdir(inc)):
+        txt = open(os.path.join(inc, h)).read()
+        txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+        txt = re.sub(r"//[^\n]*", " ", txt)
+        txt = re.sub(r"^\s*#.*$", " ", txt, flags=re.M)
+        for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(mpc_\w+)\s*\(([^;{}()]*)\)\s*;", txt):
+            params = [p.strip() for p in params.split(",")]
+            kinds = [] if params == ["void"] else [_c_kind(p) for p in params]
+            assert name not in out, name
+            out[name] = (_c_kind(ret), kinds)
+    return out
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return "ptr"
+    return {ctypes.c_int32: "i32", ctypes.c_uint32: "u32", ctypes.c_int64: "i64", ctypes.c_size_t: "size",
+            ctypes.c_double: "double"}[t]
+
+
+def binding_faults(pkg):
+    """What disagrees between _native's two tables, the headers and the libraries' exports."""
+    n = pkg._native
+    pkg._build.build_hip()
+    libs = {"libmpc.so": (pkg.engine.lib(), n.device_prototypes()),
+            "libmpc_ingest.so": (ctypes.CDLL(pkg._build.build_ingest()), n.host_prototypes())}
+    declared_by = header_prototypes()
+    faults = []
+    for name, (ret, kinds) in declared_by.items():
+        owners = [lib for lib, (L, _) in libs.items() if hasattr(L, name)]
+        if len(owners) != 1:
+            faults.append("%s: exported by %s" % (name, owners or "no library"))
+            continue
+        table = libs[owners[0]][1]
+        if name not in table:
+            faults.append("%s: declared and exported by %s, not in its table" % (name, owners[0]))
+            continue
+        restype, argtypes = table[name]
+        bound = (_ctypes_kind(restype), [_ctypes_kind(a) for a in argtypes])
+        if bound != (ret, kinds):
+            faults.append("%s: the header says %s, the table %s" % (name, (ret, kinds), bound))
+    for lib, (_, table) in libs.items():
+        faults += ["%s: in the table of %s, declared in no header" % (name, lib) for name in table if name not in declared_by]
+    return faults
+
+
+def test_header_parser():
+    """The parser sees multi-line prototypes, array parameters and every kind."""
+    p = header_prototypes()
+    assert p["mpc_verify_script"] == ("i32", ["ptr", "i64", "ptr", "i64", "i32", "i32", "ptr", "ptr", "ptr", "size"])
+    assert p["mpc_ingest_free"] == ("void", ["ptr"]) and p["mpc_version"] == ("i32", [])
+    assert p["mpc_input_layout"] == ("size", ["ptr", "i32"]) and p["mpc_last_error"] == ("ptr", [])
+    assert p["mpc_linkage_scratch_bytes"] == ("i64", ["i64", "i32"])
+    assert p["mpc_coverage_host"][1][8] == "u32" and p["mpc_run"][1] == ["ptr", "double", "double", "ptr"]
+    assert len(p) >= 53
+
+
+def test_bindings_match_headers(pkg, monkeypatch):
+    """Every function of include/*.h is in the table of the library that exports
+    it, every table entry is declared, and return type, arity and every
+    parameter's kind (pointer, 32-bit signed, uint32_t, int64_t, size_t, double,
+    void) agree.  A planted int64_t bound as c_int32 is named."""
+    assert binding_faults(pkg) == []
+    n = pkg._native
+    good = n.host_prototypes()
+    restype, argtypes = good["mpc_write_calls"]
+    assert argtypes[1] is ctypes.c_int64
+    planted = dict(good, mpc_write_calls=(restype, [argtypes[0], ctypes.c_int32] + argtypes[2:]))
+    monkeypatch.setattr(n, "host_prototypes", lambda: planted)
+    faults = binding_faults(pkg)
+    assert len(faults) == 1 and faults[0].startswith("mpc_write_calls: the header says")

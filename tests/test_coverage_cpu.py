@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import cov_util as cu
+import glue_cases as gc
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(REPO, "minion-plasmid-consensus_amd", "coverage_qc.py")
@@ -171,6 +172,36 @@ def test_ingest_errors_name_the_line(pkg, paf_files, tmp_path):
     empty = tmp_path / "empty.paf"
     empty.write_bytes(b"")
     assert pkg.coverage.read_paf(str(empty))["names"] == []
+
+
+@pytest.mark.parametrize("name", sorted(gc.PAF_FILES))
+def test_ingest_thread_cuts(pkg, name, tmp_path):
+    """1 thread and 16 threads (cuts at other line starts, several of them inside
+    one long line) read the same records."""
+    text = gc.PAF_FILES[name]
+    path = tmp_path / "in.paf"
+    path.write_text(text)
+    lines = [ln.split("\t") for ln in text.split("\n") if ln]
+    one, many = (pkg.coverage.read_paf(str(path), 1, threads=t) for t in (1, 16))
+    for d in (one, many):
+        assert d["n_lines"] == len(lines) and d["tstart"].tolist() == [int(c[7]) for c in lines]
+        assert d["cs"].tobytes()[:int(d["cs_off"][-1])].decode() == "".join(c[13][3:] for c in lines)
+        assert d["cs_off"].tolist() == np.cumsum([0] + [len(c[13]) - 3 for c in lines]).tolist()
+        assert d["names"] == (["ref"] if lines else []) and bytes(d["strand"]).decode() == "".join(c[4] for c in lines)
+    for k in ("target", "tend", "qlen", "mapq", "lengths"):
+        assert np.array_equal(one[k], many[k]), k
+
+
+@pytest.mark.parametrize("field", sorted(gc.PLAIN_INT))
+def test_plain_int_policy(pkg, field, tmp_path):
+    """An integer column is 1-18 digits and nothing else."""
+    path = tmp_path / "in.paf"
+    path.write_text(gc.paf_line("a", 12, 1, 11, "+", field, ":10"))
+    if gc.PLAIN_INT[field][1]:
+        assert pkg.coverage.read_paf(str(path))["tstart"].tolist() == [int(field)]
+    else:
+        with pytest.raises(pkg.coverage.CoverageError, match="line 1: an integer column is not plain digits"):
+            pkg.coverage.read_paf(str(path))
 
 
 # ---------------------------------------------------------------- CLI

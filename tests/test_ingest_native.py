@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import glue_cases as gc
 import golden_util as gu
 
 KEYS = ("ref", "cs", "cs_off", "tstart", "up", "up_off", "down", "down_off", "aligned")
@@ -235,3 +236,42 @@ def test_fuzz_block_scan_and_name_table(ing, seed, tmp_path):
             continue
         for k in KEYS:
             assert np.array_equal(np.asarray(c[k]), np.asarray(nat[k])), (n_threads, k)
+
+
+# ---- the pieces shared with the other PAF parsers (csrc/host_file.h) ---------------
+
+@pytest.mark.parametrize("name", sorted(gc.PAF_FILES))
+def test_thread_cuts_do_not_change_the_result(ing, name, tmp_path):
+    """1 thread and 16 threads cut the PAF at different line starts (none, or
+    several cuts inside one line): both give the Python restatement's result."""
+    ref, paf, reads = _files(tmp_path, gc.REF, gc.PAF_FILES[name], gc.READS)
+    py = ing.pack_sample_python(ref, paf, reads)
+    assert py["n_alignments"] == gc.PAF_FILES[name].count("\n") + (name == "one_line_no_newline")
+    for n_threads in (1, 16):
+        nat = ing.pack_sample_native(ref, paf, reads, n_threads=n_threads)
+        assert nat is not None, n_threads
+        for k in KEYS:
+            assert np.array_equal(nat[k], py[k]), (n_threads, k)
+        assert nat["n_alignments"] == py["n_alignments"]
+
+
+@pytest.mark.parametrize("field", sorted(gc.PLAIN_INT))
+def test_plain_int_policy(ing, field, tmp_path):
+    """What the native int() of a PAF column takes itself, refuses like Python, or leaves to Python."""
+    want = gc.PLAIN_INT[field][0]
+    try:
+        int(field)
+        python_takes = True
+    except ValueError:
+        python_takes = False
+    assert python_takes == (want != "error")
+    paths = _files(tmp_path, gc.REF, gc.paf_line("a", 12, field, 11, "+", 0, ":10"), gc.READS)
+    if want == "error":
+        for fn in (ing.pack_sample_native, ing.pack_sample_python):
+            with pytest.raises(ing.IngestError, match="ValueError"):
+                fn(*paths)
+    elif want == "python":
+        assert ing.pack_sample_native(*paths) is None
+        assert _same(ing, *paths, expect_native=False) is not None
+    else:
+        assert _same(ing, *paths) is not None

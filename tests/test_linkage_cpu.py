@@ -77,6 +77,18 @@ def test_host_refuses_bad_tables_untouched(pkg):
     assert alleles.tolist() == [1, 0, 0] and status.tolist() == [0, 0] and pair.reshape(3, 3, 8, 8)[0, 1, 1, 0] == 1
 
 
+def test_last_errors_are_per_tool(pkg):
+    """A failed linkage call leaves the coverage message of the same thread as it was."""
+    L = pkg.linkage.host_lib()
+    p = np.zeros(64, np.int64).ctypes.data
+    assert L.mpc_coverage_host(p, p, p, p, -1, p, p, 1, 0, p, p, p, 1, None) == -1
+    said = L.mpc_coverage_last_error()
+    assert said == b"mpc_coverage_host: n_records outside [0, 2^31)"
+    assert L.mpc_linkage_host(p, p, p, p, 0, p, 0, p, p, 1, p, p, p, 1) == -1
+    assert L.mpc_linkage_last_error() == b"mpc_linkage_host: n_samples < 1"
+    assert L.mpc_coverage_last_error() == said
+
+
 def test_select_sites_keeps_the_highest_fractions(pkg):
     rows = np.zeros((11, 4), np.uint32)  # one 10-base target, depth 100 everywhere
     rows[:10, 0] = 100

@@ -10,6 +10,8 @@ import random
 
 import pytest
 
+import glue_cases as gc
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "golden_pseudopair")
 
@@ -83,3 +85,17 @@ def test_random_native_vs_python(pp, seed, tmp_path):
         pairs, nf, nr, nfk, nrk = pp.pseudopair_python(str(paf), m)
         assert (st.n_fwd, st.n_rev, st.n_fwd_kept, st.n_rev_kept) == (nf, nr, nfk, nrk)
         assert (tmp_path / "n.txt").read_text() == "".join("%s %s\n" % x for x in pairs)
+
+
+@pytest.mark.parametrize("field", sorted(gc.PLAIN_INT))
+def test_plain_int_policy(pp, field, tmp_path):
+    """[+-] and 1-18 digits are read natively (with the value Python reads); every other form is declined."""
+    paf = tmp_path / "in.paf"
+    paf.write_text(gc.paf_line("a", 12, field, 11, "+", 0, ":10") + gc.B)
+    st = pp.pseudopair_native(str(paf), 7, str(tmp_path / "n.txt"))
+    if not gc.PLAIN_INT[field][2]:
+        assert st is None
+        return
+    pairs, nf, nr, nfk, nrk = pp.pseudopair_python(str(paf), 7)
+    assert (st.n_fwd, st.n_rev, st.n_fwd_kept, st.n_rev_kept) == (nf, nr, nfk, nrk) == (1, 1, int(11 - int(field) >= 7), 1)
+    assert (tmp_path / "n.txt").read_text() == "".join("%s %s\n" % x for x in pairs)
