@@ -13,6 +13,8 @@ Modules
   coverage per-position depth / deletion / mismatch / insertion profile from the PAF (K_covparse)
   linkage  per-read alleles at variable sites and their pairwise co-occurrence (K_lnkparse, K_lnkpair)
   align    exact read-to-assembly alignment to a cs-tagged PAF (K_arevcomp, K_vscan, K_atrace)
+  _cli     what the command-line tools below share: status lines, banner, argparse types, error line,
+           output files, verdict and exit status (standard library only; not imported here)
   mapped_paf_read_parser  the drop-in CLI
   verify_consensus        the "Check the results" CLI
   coverage_qc             the coverage criterion CLI

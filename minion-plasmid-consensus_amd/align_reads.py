@@ -25,30 +25,14 @@ import argparse
 import importlib
 import os
 import sys
-import time
 
+if __package__:
+    from . import _cli
+else:  # run by path: sys.path[0] is this directory
+    import _cli
+
+statprint = _cli.statprint
 TITLE = "Align Reads"
-
-
-def statprint(msg, msg_type="STATUS"):
-    print("{} [{}]: {}".format(msg_type, time.strftime("%Y/%m/%d %T"), msg), flush=True)
-
-
-def _pkg():
-    if __package__:
-        return importlib.import_module(__package__)
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    return importlib.import_module(os.path.basename(here))
-
-
-def _device(text):
-    if text == "cpu":
-        return text
-    try:
-        return int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError("a HIP device index or 'cpu'")
 
 
 def _fraction(text):
@@ -68,7 +52,7 @@ def build_parser():
     p.add_argument("--paf", required=True, help="PAF output file")
     p.add_argument("--max-error", type=_fraction, default=0.2, help="Largest distance of a mapped read, as a fraction of its length")
     p.add_argument("--summary", help="Summary output file (TSV)")
-    p.add_argument("--device", type=_device, default=0, help="HIP device index, or 'cpu' for the host path")
+    p.add_argument("--device", type=_cli.device_arg, default=0, help="HIP device index, or 'cpu' for the host path")
     return p
 
 
@@ -81,10 +65,9 @@ def _discard(path):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    pkg = _pkg()
+    pkg = _cli.package(__file__, __package__)
     align = importlib.import_module(pkg.__name__ + ".align")
-    statprint("Aligning {} to {} on {}...".format(args.reads, args.ref,
-                                                  "the host" if args.device == "cpu" else "device {}".format(args.device)))
+    statprint("Aligning {} to {} on {}...".format(args.reads, args.ref, _cli.place(args.device)))
     tmp = "{}.tmp.{}".format(args.paf, os.getpid())  # renamed once complete: no PAF on rejected input
     try:
         with open(tmp, "wb") as f:
@@ -95,8 +78,7 @@ def main(argv=None):
                 f.write(align.summary_text(res["summary"]))
     except (align.AlignError, pkg.engine.MpcError, OSError) as e:
         _discard(tmp)
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
+        return _cli.fail(e)
     except BaseException:
         _discard(tmp)
         raise

@@ -207,6 +207,33 @@ def derived(st, lo, hi):
                 error_rate=err / (st[ST_MATCH] + err) if st[ST_MATCH] + err else 0.0)
 
 
+def expected_core(expected, err):
+    """(adapted length, c0, c1) of the adapter-padded FASTA `expected`: its
+    upper-case plasmid core is [c0, c1).  None without a file; what
+    verify.read_expected refuses raises err."""
+    if expected is None:
+        return None
+    from . import verify
+    try:
+        adapted, c0, c1 = verify.read_expected(expected)
+    except verify.VerifyError as e:
+        raise err(str(e))
+    return len(adapted), c0, c1
+
+
+def target_regions(path, names, lengths, core, region, err):
+    """[(lo, hi)] of a PAF's targets: the core (expected_core) of a target as
+    long as the adapted sequence, else `region`, else the whole target.  A
+    region outside its target raises err."""
+    out = []
+    for name, L in zip(names, lengths):
+        lo, hi = core[1:] if core and L == core[0] else region if region else (0, L)
+        if not 0 <= lo <= hi <= L:
+            raise err("{}: target {}: region {}:{} is outside 0:{}".format(path, name, lo, hi, L))
+        out.append((lo, hi))
+    return out
+
+
 def qc(paf_paths, expected=None, region=None, all_alignments=False, min_mean_coverage=MIN_MEAN_COVERAGE, min_depth=0,
        device=0, threads=0):
     """dict(blocks, verdict): one block per (paf, target) -- every PAF and every
@@ -214,24 +241,13 @@ def qc(paf_paths, expected=None, region=None, all_alignments=False, min_mean_cov
     as long as it is measured over its upper-case plasmid core.  region: (lo,
     hi), 0-based half-open, for every target.  verdict: "PASS" iff every block
     has mean depth >= min_mean_coverage and no region position below min_depth."""
-    core = None
-    if expected is not None:
-        from . import verify
-        try:
-            adapted, c0, c1 = verify.read_expected(expected)
-        except verify.VerifyError as e:
-            raise CoverageError(str(e))
-        core = (len(adapted), c0, c1)
+    core = expected_core(expected, CoverageError)
     pafs = [(p, read_paf(p, 1 if all_alignments else 0, threads)) for p in paf_paths]
     lengths, regions, owner = [], [], []
     for p, d in pafs:
-        for name, L in zip(d["names"], d["lengths"]):
-            lo, hi = (core[1], core[2]) if core and L == core[0] else region if region else (0, L)
-            if not 0 <= lo <= hi <= L:
-                raise CoverageError("{}: target {}: region {}:{} is outside 0:{}".format(p, name, lo, hi, L))
-            lengths.append(L)
-            regions.append((lo, hi))
-            owner.append((p, name))
+        regions += target_regions(p, d["names"], d["lengths"], core, region, CoverageError)
+        lengths += d["lengths"]
+        owner += [(p, name) for name in d["names"]]
     if not lengths:
         raise CoverageError("no alignment in {}".format(", ".join(map(str, paf_paths))))
     sample_base = np.cumsum([0] + [len(d["names"]) for _, d in pafs])

@@ -27,45 +27,20 @@ output file) on unreadable or invalid input.
 """
 import argparse
 import importlib
-import os
 import sys
-import time
 
+if __package__:
+    from . import _cli
+else:  # run by path: sys.path[0] is this directory
+    import _cli
+
+statprint = _cli.statprint
 TITLE = "Coverage QC"
 REPORT_KEYS = ("paf", "target", "length", "records", "region", "mean_depth", "sd_depth", "min_depth",
                "min_depth_position", "max_depth", "positions_below_min_depth", "mean_deleted", "match_bases",
                "mismatch_bases", "inserted_bases", "deleted_bases", "insertion_events", "deletion_events", "error_rate",
                "mean_mapq", "mean_read_length", "plus_strand_records", "minus_strand_records")
 PER_BASE_HEADER = "paf\ttarget\tpos\tdepth\tdeleted\tmismatch\tinsertion\n"
-
-
-def statprint(msg, msg_type="STATUS"):
-    print("{} [{}]: {}".format(msg_type, time.strftime("%Y/%m/%d %T"), msg), flush=True)
-
-
-def _pkg():
-    if __package__:
-        return importlib.import_module(__package__)
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    return importlib.import_module(os.path.basename(here))
-
-
-def _device(text):
-    if text == "cpu":
-        return text
-    try:
-        return int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError("a HIP device index or 'cpu'")
-
-
-def _region(text):
-    try:
-        lo, hi = (int(x) for x in text.split(":"))
-    except ValueError:
-        raise argparse.ArgumentTypeError("START:END (0-based, half-open)")
-    return lo, hi
 
 
 def build_parser():
@@ -75,31 +50,22 @@ def build_parser():
     p.add_argument("--per-base", help="Per-position output file (TSV)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--expected", help="Adapter-padded reference fasta: measure the upper-case plasmid core")
-    g.add_argument("--region", type=_region, help="START:END (0-based, half-open) of every target")
+    g.add_argument("--region", type=_cli.region_arg, help="START:END (0-based, half-open) of every target")
     p.add_argument("--all-alignments", action="store_true", help="Keep every PAF line, not the first per read name")
     p.add_argument("--min-mean-coverage", type=float, default=100000.0, help="Mean depth every target needs to PASS")
     p.add_argument("--min-depth", type=int, default=0, help="Depth every region position needs to PASS")
-    p.add_argument("--device", type=_device, default=0, help="HIP device index, or 'cpu' for the host walk")
+    p.add_argument("--device", type=_cli.device_arg, default=0, help="HIP device index, or 'cpu' for the host walk")
     p.add_argument("--strict", action="store_true", help="Exit status 2 when the verdict is FAIL")
     return p
 
 
-def block_values(b):
-    cov = importlib.import_module(_pkg().__name__ + ".coverage")
+def block_values(cov, b):
     st = b["stats"]
     return (b["paf"], b["target"], b["length"], b["records"], "{}:{}".format(*b["region"]), repr(b["mean"]),
             repr(b["sd"]), st[cov.ST_MIN], b["min_position"], st[cov.ST_MAX], st[cov.ST_BELOW], repr(b["mean_deleted"]),
             st[cov.ST_MATCH], st[cov.ST_MISMATCH], st[cov.ST_INS_BASES], st[cov.ST_DEL_BASES], st[cov.ST_INS_EVENTS],
             st[cov.ST_DEL_EVENTS], repr(b["error_rate"]), repr(b["mean_mapq"]), repr(b["mean_read_length"]), b["plus"],
             b["minus"])
-
-
-def report_text(res):
-    out = []
-    for b in res["blocks"]:
-        out += ["{}\t{}\n".format(k, v) for k, v in zip(REPORT_KEYS, block_values(b))]
-    out.append("verdict\t{}\n".format(res["verdict"]))
-    return "".join(out)
 
 
 def per_base_text(res):
@@ -112,37 +78,24 @@ def per_base_text(res):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    pkg = _pkg()
+    pkg = _cli.package(__file__, __package__)
     cov = importlib.import_module(pkg.__name__ + ".coverage")
     if args.min_depth < 0 or args.min_depth >= 2 ** 32:
-        print("Error: --min-depth must be in [0, 2^32)", file=sys.stderr)
-        return 1
-    statprint("Walking {} PAF file(s) on {}...".format(
-        len(args.paf), "the host" if args.device == "cpu" else "device {}".format(args.device)))
+        return _cli.fail("--min-depth must be in [0, 2^32)")
+    statprint("Walking {} PAF file(s) on {}...".format(len(args.paf), _cli.place(args.device)))
     try:
         res = cov.qc(args.paf, expected=args.expected, region=args.region, all_alignments=args.all_alignments,
                      min_mean_coverage=args.min_mean_coverage, min_depth=args.min_depth, device=args.device)
-        report = report_text(res)
-        per_base = per_base_text(res) if args.per_base else None
-    except (cov.CoverageError, pkg.engine.MpcError, OSError, UnicodeDecodeError) as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
-    for b in res["blocks"]:
-        st = b["stats"]
-        statprint("{} [{}]: mean {:,.1f}x, minimum {:,}x at position {:,}, {:,} records".format(
-            b["paf"], b["target"], b["mean"], st[cov.ST_MIN], b["min_position"], b["records"]))
-    try:
-        with open(args.report, "w") as f:
-            f.write(report)
+        report = _cli.key_value_report(REPORT_KEYS, (block_values(cov, b) for b in res["blocks"]), res["verdict"])
+        texts = [(args.report, report)]
         if args.per_base:
-            with open(args.per_base, "w") as f:
-                f.write(per_base)
-    except OSError as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
-    statprint("Coverage: {}".format(res["verdict"]))
-    statprint("Done.")
-    return 2 if args.strict and res["verdict"] == "FAIL" else 0
+            texts.append((args.per_base, per_base_text(res)))
+    except (cov.CoverageError, pkg.engine.MpcError, OSError, UnicodeDecodeError) as e:
+        return _cli.fail(e)
+    for b in res["blocks"]:
+        statprint("{} [{}]: mean {:,.1f}x, minimum {:,}x at position {:,}, {:,} records".format(
+            b["paf"], b["target"], b["mean"], b["stats"][cov.ST_MIN], b["min_position"], b["records"]))
+    return _cli.write_texts(texts) or _cli.verdict_exit("Coverage", args.strict, res["verdict"])
 
 
 if __name__ == "__main__":

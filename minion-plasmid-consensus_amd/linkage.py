@@ -229,14 +229,7 @@ def qc(paf_paths, sites=None, min_minor_fraction=MIN_MINOR_FRACTION, min_minor_c
     """dict(blocks, verdict): one block per (paf, target).  Per PAF: one
     coverage.run, one site selection (or `sites` = {target: keys}) and one
     linkage run.  verdict: "PASS" iff no site pair of any target is linked."""
-    core = None
-    if expected is not None:
-        from . import verify
-        try:
-            adapted, c0, c1 = verify.read_expected(expected)
-        except verify.VerifyError as e:
-            raise LinkageError(str(e))
-        core = (len(adapted), c0, c1)
+    core = coverage.expected_core(expected, LinkageError)
     blocks, linked_any, named = [], False, set()
     for path in paf_paths:
         try:
@@ -246,12 +239,7 @@ def qc(paf_paths, sites=None, min_minor_fraction=MIN_MINOR_FRACTION, min_minor_c
         lengths, names = d["lengths"], d["names"]
         if not lengths:
             raise LinkageError("no alignment in {}".format(path))
-        regions = []
-        for name, L in zip(names, lengths):
-            lo, hi = (core[1], core[2]) if core and L == core[0] else region if region else (0, L)
-            if not 0 <= lo <= hi <= L:
-                raise LinkageError("{}: target {}: region {}:{} is outside 0:{}".format(path, name, lo, hi, L))
-            regions.append((lo, hi))
+        regions = coverage.target_regions(path, names, lengths, core, region, LinkageError)
         batch = (d["cs"], d["cs_off"], d["tstart"], d["target"], lengths)
         try:
             if sites is None:

@@ -39,45 +39,20 @@ output file) on unreadable or invalid input.
 """
 import argparse
 import importlib
-import os
 import sys
-import time
 
+if __package__:
+    from . import _cli
+else:  # run by path: sys.path[0] is this directory
+    import _cli
+
+statprint = _cli.statprint
 TITLE = "Linkage QC"
 REPORT_KEYS = ("paf", "target", "length", "records", "region", "sites", "sites_dropped", "site_list", "major_alleles",
                "minor_counts", "pairs", "linked_pairs", "max_r2", "max_r2_pair", "haplotypes", "records_covered_everywhere")
 PAIRS_HEADER = "paf\ttarget\tsite_i\tsite_j\tn\tminor_i\tminor_j\tminor_both\tr2\tlinked\n"
 HAPLOTYPES_HEADER = "paf\ttarget\thaplotype\tcount\n"
 _ALLELE = "0.ACGTN"
-
-
-def statprint(msg, msg_type="STATUS"):
-    print("{} [{}]: {}".format(msg_type, time.strftime("%Y/%m/%d %T"), msg), flush=True)
-
-
-def _pkg():
-    if __package__:
-        return importlib.import_module(__package__)
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    return importlib.import_module(os.path.basename(here))
-
-
-def _device(text):
-    if text == "cpu":
-        return text
-    try:
-        return int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError("a HIP device index or 'cpu'")
-
-
-def _region(text):
-    try:
-        lo, hi = (int(x) for x in text.split(":"))
-    except ValueError:
-        raise argparse.ArgumentTypeError("START:END (0-based, half-open)")
-    return lo, hi
 
 
 def build_parser():
@@ -91,12 +66,12 @@ def build_parser():
     p.add_argument("--min-minor-count", type=int, default=10, help="Minor observations a selected site needs")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--expected", help="Adapter-padded reference fasta: select inside the upper-case plasmid core")
-    g.add_argument("--region", type=_region, help="START:END (0-based, half-open) of every target")
+    g.add_argument("--region", type=_cli.region_arg, help="START:END (0-based, half-open) of every target")
     p.add_argument("--all-alignments", action="store_true", help="Keep every PAF line, not the first per read name")
     p.add_argument("--min-r2", type=float, default=0.1, help="r2 a linked pair needs")
     p.add_argument("--min-joint", type=int, default=10, help="Records minor at both sites a linked pair needs")
     p.add_argument("--max-haplotypes", type=int, default=50, help="Haplotypes listed per target")
-    p.add_argument("--device", type=_device, default=0, help="HIP device index, or 'cpu' for the host walk")
+    p.add_argument("--device", type=_cli.device_arg, default=0, help="HIP device index, or 'cpu' for the host walk")
     p.add_argument("--strict", action="store_true", help="Exit status 2 when the verdict is FAIL")
     return p
 
@@ -114,14 +89,6 @@ def block_values(lnk, b):
             ",".join(labels), ",".join(_allele(m, k) for m, k in zip(b["majors"], b["keys"])), ",".join(map(str, minor)),
             len(b["pairs"]), sum(1 for _, _, st in b["pairs"] if st["linked"]), repr(best[2]["r2"]) if best else repr(0.0),
             "{}/{}".format(labels[best[0]], labels[best[1]]) if best else "", len(b["haplotypes"]), covered)
-
-
-def report_text(lnk, res):
-    out = []
-    for b in res["blocks"]:
-        out += ["{}\t{}\n".format(k, v) for k, v in zip(REPORT_KEYS, block_values(lnk, b))]
-    out.append("verdict\t{}\n".format(res["verdict"]))
-    return "".join(out)
 
 
 def pairs_text(lnk, res):
@@ -144,41 +111,30 @@ def haplotypes_text(res, limit):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    pkg = _pkg()
+    pkg = _cli.package(__file__, __package__)
     lnk = importlib.import_module(pkg.__name__ + ".linkage")
     cov = importlib.import_module(pkg.__name__ + ".coverage")
     if args.min_minor_count < 0 or args.min_joint < 0 or args.max_haplotypes < 0 or not 0.0 <= args.min_minor_fraction <= 1.0:
-        print("Error: counts must be >= 0 and --min-minor-fraction in [0, 1]", file=sys.stderr)
-        return 1
-    statprint("Reading alleles of {} PAF file(s) on {}...".format(
-        len(args.paf), "the host" if args.device == "cpu" else "device {}".format(args.device)))
+        return _cli.fail("counts must be >= 0 and --min-minor-fraction in [0, 1]")
+    statprint("Reading alleles of {} PAF file(s) on {}...".format(len(args.paf), _cli.place(args.device)))
     try:
         sites = lnk.read_sites(args.sites) if args.sites else None
         res = lnk.qc(args.paf, sites=sites, min_minor_fraction=args.min_minor_fraction, min_minor_count=args.min_minor_count,
                      expected=args.expected, region=args.region, all_alignments=args.all_alignments, min_r2=args.min_r2,
                      min_joint=args.min_joint, device=args.device)
-        outputs = [(args.report, report_text(lnk, res))]
+        report = _cli.key_value_report(REPORT_KEYS, (block_values(lnk, b) for b in res["blocks"]), res["verdict"])
+        texts = [(args.report, report)]
         if args.pairs:
-            outputs.append((args.pairs, pairs_text(lnk, res)))
+            texts.append((args.pairs, pairs_text(lnk, res)))
         if args.haplotypes:
-            outputs.append((args.haplotypes, haplotypes_text(res, args.max_haplotypes)))
+            texts.append((args.haplotypes, haplotypes_text(res, args.max_haplotypes)))
     except (lnk.LinkageError, cov.CoverageError, pkg.engine.MpcError, OSError, UnicodeDecodeError) as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
+        return _cli.fail(e)
     for b in res["blocks"]:
         statprint("{} [{}]: {:,} sites, {:,} of {:,} pairs linked, {:,} records".format(
             b["paf"], b["target"], len(b["keys"]), sum(1 for _, _, st in b["pairs"] if st["linked"]), len(b["pairs"]),
             b["records"]))
-    try:
-        for path, text in outputs:
-            with open(path, "w") as f:
-                f.write(text)
-    except OSError as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
-    statprint("Linkage: {}".format(res["verdict"]))
-    statprint("Done.")
-    return 2 if args.strict and res["verdict"] == "FAIL" else 0
+    return _cli.write_texts(texts) or _cli.verdict_exit("Linkage", args.strict, res["verdict"])
 
 
 if __name__ == "__main__":

@@ -24,23 +24,16 @@ Extra, optional flags (defaults keep the reference behaviour):
 """
 import argparse
 import importlib
-import os
 import sys
 import time
 
+if __package__:
+    from . import _cli
+else:  # run by path: sys.path[0] is this directory
+    import _cli
+
+statprint = _cli.statprint
 TITLE = "Mapped PAF Read Parser"
-
-
-def statprint(msg, msg_type="STATUS"):
-    print("{} [{}]: {}".format(msg_type, time.strftime("%Y/%m/%d %T"), msg), flush=True)
-
-
-def _pkg():
-    if __package__:
-        return importlib.import_module(__package__)
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    return importlib.import_module(os.path.basename(here))
 
 
 def build_parser():
@@ -171,17 +164,9 @@ def main(argv=None, timings=None):
     if args.gpus < 1:
         parser.error("--gpus must be at least 1")
     tm = timings if timings is not None else {}
-    pkg = _pkg()
+    pkg = _cli.package(__file__, __package__)
     ingest, engine, writers = pkg.ingest, pkg.engine, pkg.writers
-    print("=======================================================")
-    print("Python version: {}".format(sys.version))
-    print("Python environment: {}".format(sys.prefix))
-    print("Server: {}".format(os.uname()[1]))
-    print("Current directory: {}".format(os.getcwd()))
-    print("Command: {}".format(" ".join(sys.argv)))
-    print("Time: {}".format(time.strftime("%Y/%m/%d %T")))
-    print("Engine: libmpc (HIP, gfx950)")
-    print("=======================================================\n")
+    _cli.banner(["Engine: libmpc (HIP, gfx950)"])
     # (ref, paf, reads, consensus, chromat, accuracies) per job
     jobs = [] if (args.job and args.REF is None) else \
         [(args.REF, args.PAF, args.READS, args.consensus, args.chromat, args.accuracies)]
@@ -196,12 +181,8 @@ def main(argv=None, timings=None):
             raise ingest.IngestError("TypeError: --min_depth_factor is required")
         if args.GLOBAL_THRESHOLD_FACTOR is None and any(len(r["count"]) or r["max_depth"] for r in results):
             raise ingest.IngestError("TypeError: --global_threshold_factor is required")  # (:421)
-    except (ingest.IngestError, engine.DataError, OSError, UnicodeDecodeError) as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
-    except engine.MpcError as e:  # input past the engine's limits (e.g. a reference over 2^22 - 2 bases)
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
+    except (ingest.IngestError, engine.DataError, engine.MpcError, OSError, UnicodeDecodeError) as e:
+        return _cli.fail(e)  # (MpcError: input past the engine's limits, e.g. a reference over 2^22 - 2 bases)
     t2 = time.perf_counter()
     for (ref, paf, _, c, ch, acc), res in zip(jobs, results):
         statprint("Max depth is {}.".format(res["max_depth"]))
@@ -210,16 +191,14 @@ def main(argv=None, timings=None):
         try:
             writers.write_outputs(res, c, ch, acc)
         except OSError as e:  # WriteError included: the reference's open()/write() raise -> exit 1
-            print("Error: {}".format(e), file=sys.stderr)
-            return 1
+            return _cli.fail(e)
     tm["write"] = time.perf_counter() - t2
     for src, dst in args.revcomp:
         statprint("Reverse-complementing {} into {}...".format(src, dst))
         try:
             writers.revcomp_consensus(src, dst)
         except (writers.RevcompError, OSError, UnicodeDecodeError) as e:
-            print("Error: {}".format(e), file=sys.stderr)
-            return 1
+            return _cli.fail(e)
     statprint("Done.")
     tm["main"] = time.perf_counter() - t_main
     return 0

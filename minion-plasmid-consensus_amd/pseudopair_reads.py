@@ -23,20 +23,22 @@ the script fails before it opens the output.
 """
 import argparse
 import ctypes
+import functools
+import importlib
 import os
 import sys
-import time
 
+if __package__:
+    from . import _cli
+else:  # run by path: sys.path[0] is this directory
+    import _cli
+
+statprint = functools.partial(_cli.statprint, colour=True)  # as the reference prints it
 TITLE = "PseudoPair Reads"
 
 
 class PairError(Exception):
     """An input the reference rejects (exit status 1)."""
-
-
-def statprint(msg, msg_type="STATUS"):
-    print("\033[1;37;40m{}\033[0m \033[1;34;40m[{}]\033[0m: {}".format(msg_type, time.strftime("%Y/%m/%d %T"), msg),
-          flush=True)
 
 
 def pseudopair_python(paf_path, min_align_length):
@@ -77,11 +79,12 @@ class _Stats(ctypes.Structure):
 def pseudopair_native(paf_path, min_align_length, out_path, n_threads=0):
     """The whole tool through libmpc_ingest.so: writes out_path and returns the
     stats, None when the native parser declines the input, or raises PairError."""
-    from . import ingest
-    L = ingest._native()
+    pkg = _cli.package(__file__, __package__)
+    L = pkg.ingest._native()
     if L is None:
         return None
-    st = _Stats()
+    # the package's _Stats is the one the binding table names; run by path, this file's own is a second class
+    st = importlib.import_module(pkg.__name__ + ".pseudopair_reads")._Stats()
     L.mpc_pseudopair(os.fsencode(paf_path), int(min_align_length or 0), 0 if min_align_length is None else 1,
                      os.fsencode(out_path), int(n_threads), ctypes.byref(st))
     if st.status == 2:
@@ -103,14 +106,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    print("=======================================================")
-    print("Python version: {}".format(sys.version))
-    print("Python environment: {}".format(sys.prefix))
-    print("Server: {}".format(os.uname()[1]))
-    print("Current directory: {}".format(os.getcwd()))
-    print("Command: {}".format(" ".join(sys.argv)))
-    print("Time: {}".format(time.strftime("%Y/%m/%d %T")))
-    print("=======================================================\n")
+    _cli.banner()
     statprint("Parsing PAF file...")
     try:
         st = pseudopair_native(args.paf, args.min_align_length, args.pseudopairs)
@@ -119,8 +115,7 @@ def main(argv=None):
         else:
             pairs, *counts = pseudopair_python(args.paf, args.min_align_length)
     except (PairError, OSError, UnicodeDecodeError) as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
+        return _cli.fail(e)
     statprint("There are {} forward reads and {} reverse reads.".format(counts[0], counts[1]))
     statprint("Removing reads with short alignments...")
     statprint("There are {} forward reads and {} reverse reads.".format(counts[2], counts[3]))

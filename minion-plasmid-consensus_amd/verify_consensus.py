@@ -25,33 +25,16 @@ output file) on unreadable or invalid input.
 """
 import argparse
 import importlib
-import os
 import sys
-import time
 
+if __package__:
+    from . import _cli
+else:  # run by path: sys.path[0] is this directory
+    import _cli
+
+statprint = _cli.statprint
 TITLE = "Verify Consensus"
 REPORT_HEADER = "consensus\tregion\texpected_len\tconsensus_len\tstart\tend\tdistance\tmismatches\tinsertions\tdeletions\tcigar\n"
-
-
-def statprint(msg, msg_type="STATUS"):
-    print("{} [{}]: {}".format(msg_type, time.strftime("%Y/%m/%d %T"), msg), flush=True)
-
-
-def _pkg():
-    if __package__:
-        return importlib.import_module(__package__)
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    return importlib.import_module(os.path.basename(here))
-
-
-def _device(text):
-    if text == "cpu":
-        return text
-    try:
-        return int(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError("a HIP device index or 'cpu'")
 
 
 def build_parser():
@@ -61,7 +44,7 @@ def build_parser():
     p.add_argument("--accuracies", nargs="*", default=[], help="Per-base accuracies files")
     p.add_argument("--report", required=True, help="Report output file (TSV)")
     p.add_argument("--edits", help="Edit list output file (TSV)")
-    p.add_argument("--device", type=_device, default=0, help="HIP device index, or 'cpu' for the host scan")
+    p.add_argument("--device", type=_cli.device_arg, default=0, help="HIP device index, or 'cpu' for the host scan")
     p.add_argument("--strict", action="store_true", help="Exit status 2 when the verdict is FAIL")
     return p
 
@@ -85,31 +68,21 @@ def edits_text(res):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    pkg = _pkg()
+    pkg = _cli.package(__file__, __package__)
     verify = importlib.import_module(pkg.__name__ + ".verify")
     statprint("Aligning {} consensus file(s) with {} on {}...".format(
-        len(args.consensus), args.expected, "the host" if args.device == "cpu" else "device {}".format(args.device)))
+        len(args.consensus), args.expected, _cli.place(args.device)))
     try:
         res = verify.verify(args.expected, args.consensus, args.accuracies, device=args.device)
-        report, edit_lines = report_text(res), edits_text(res)
+        texts = [(args.report, report_text(res))]
+        if args.edits:
+            texts.append((args.edits, edits_text(res)))
     except (verify.VerifyError, pkg.engine.MpcError, OSError, UnicodeDecodeError) as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
+        return _cli.fail(e)
     for r in res["rows"]:
         statprint("{} [{}]: distance {} over consensus [{}, {})".format(r["consensus"], r["region"], r["distance"],
                                                                         r["start"], r["end"]))
-    try:
-        with open(args.report, "w") as f:
-            f.write(report)
-        if args.edits:
-            with open(args.edits, "w") as f:
-                f.write(edit_lines)
-    except OSError as e:
-        print("Error: {}".format(e), file=sys.stderr)
-        return 1
-    statprint("Verdict: {}".format(res["verdict"]))
-    statprint("Done.")
-    return 2 if args.strict and res["verdict"] == "FAIL" else 0
+    return _cli.write_texts(texts) or _cli.verdict_exit("Verdict", args.strict, res["verdict"])
 
 
 if __name__ == "__main__":

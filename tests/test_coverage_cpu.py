@@ -273,6 +273,38 @@ def test_cli_expected_restricts_to_the_core(pkg, paf_files, tmp_path):
     assert "region\t40:560" in rep.read_text().splitlines()
 
 
+# ---------------------------------------------------------------- the region rule of coverage.qc and linkage.qc
+
+@pytest.mark.parametrize("err", ["coverage.CoverageError", "linkage.LinkageError"])
+def test_target_regions(pkg, err, tmp_path):
+    mod, cls = err.split(".")
+    err = getattr(getattr(pkg, mod), cls)
+    names, lengths = ["a", "b", "c"], [600, 599, 601]
+    regions = lambda core, region: pkg.coverage.target_regions("x.paf", names, lengths, core, region, err)
+    assert regions(None, None) == [(0, 600), (0, 599), (0, 601)]              # the whole target by default
+    assert regions(None, (5, 90)) == [(5, 90)] * 3                            # --region, for every target
+    assert regions((600, 40, 560), None) == [(40, 560), (0, 599), (0, 601)]   # the core only at equal length
+    assert regions((600, 40, 560), (5, 90)) == [(40, 560), (5, 90), (5, 90)]  # (the CLI excludes the two; the API does not)
+    assert regions((7, 1, 2), (0, 599)) == [(0, 599)] * 3 and regions(None, (599, 599)) == [(599, 599)] * 3
+    for region, name, L in (((-1, 5), "a", 600), ((7, 6), "a", 600), ((5, 600), "b", 599)):  # lo < 0, lo > hi, hi > L
+        with pytest.raises(err) as e:
+            regions(None, region)
+        assert str(e.value) == "x.paf: target {}: region {}:{} is outside 0:{}".format(name, region[0], region[1], L)
+    with pytest.raises(err) as e:  # a core outside a target of its length is refused like a region
+        regions((601, 5, 602), None)
+    assert str(e.value) == "x.paf: target c: region 5:602 is outside 0:601"
+    # expected_core: None without a file, (adapted length, c0, c1), and verify's refusal under the caller's class
+    exp = tmp_path / "x.fasta"
+    exp.write_bytes(b">x\nacgtGGTTACac\n")
+    assert pkg.coverage.expected_core(None, err) is None and pkg.coverage.expected_core(str(exp), err) == (12, 4, 10)
+    exp.write_bytes(b">x\nacgt\n")
+    with pytest.raises(pkg.verify.VerifyError) as plain:
+        pkg.verify.read_expected(str(exp))
+    with pytest.raises(err) as e:
+        pkg.coverage.expected_core(str(exp), err)
+    assert str(e.value) == str(plain.value) and type(e.value) is err
+
+
 # ---------------------------------------------------------------- sanitizers
 
 DRIVER = r"""
