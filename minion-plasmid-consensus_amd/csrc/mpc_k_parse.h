@@ -514,7 +514,8 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
   uint32_t* del_l = uni + nsub;
   for (int k = threadIdx.x; !big && k < parse_hl_words(n); k += blockDim.x) hl[k] = 0;
   for (int k = threadIdx.x; !big && k < nbk; k += blockDim.x) bkw[k] = kPgInit;  // (mode 4: K_clear)
-  if (threadIdx.x == 0) { *cnext = (uint32_t)nw; *npg = 0u; cnext[2] = 0u; }  // chunks 0..nw-1 go to waves 0..nw-1
+  // chunks 0..nw-1 go to waves 0..nw-1 (the counter runs in units of 64: take_chunk)
+  if (threadIdx.x == 0) { *cnext = (uint32_t)nw * 64u; *npg = 0u; cnext[2] = 0u; }
   const int nch = wk.w;
   for (int k = threadIdx.x; k <= nch; k += blockDim.x) {
     const int32_t r = a.wave_tab[(int64_t)blockIdx.x * (kMaxCh + 1) + k];
@@ -568,12 +569,17 @@ __global__ __launch_bounds__(kMaxPW * 64) void K_parse(ParseArgs a) {
   // time: profiles/r03_stamps).  The chunk table sits in LDS (one load per
   // chunk bound per workgroup).  A chunk is a stream of its own: event
   // regions, i_end.
-  // take the next chunk: every lane adds (lane 0 one, the others zero), so no
-  // divergent region guards the atomic (a lane-0-only atomic in the loop head
-  // was compiled into a loop exit that only lane 0 took: the wave never left)
+  // take the next chunk: every lane of the wave adds 1, so the counter runs in
+  // units of 64 (the wave is whole here: blocks are whole waves, and the chunk
+  // loop is wave-uniform).  No divergent region guards the atomic (a
+  // lane-0-only atomic in the loop head was compiled into a loop exit that
+  // only lane 0 took: the wave never left), and the value added is uniform: a
+  // per-lane value (lane 0 one, the others zero) was compiled into a scalar
+  // loop over all 64 lanes, ~500 instructions per chunk taken, where this is
+  // one lane count and one add
   auto take_chunk = [&]() {
-    const uint32_t v = atomicAdd(cnext, l == 0 ? 1u : 0u);
-    return uniform_i32(__builtin_amdgcn_readlane((int)v, 0));
+    const uint32_t v = atomicAdd(cnext, 1u);
+    return uniform_i32((int)(v >> 6));  // (the first lane's: the counter before the add)
   };
   // deferred placement: the wave's queue of (bucket, event word) in LDS, a ring
   // of kDefQ entries between dq_tail and dq_head (wave-uniform counters); a

@@ -2,7 +2,8 @@
 """Parse phase (K_clear + K_parse [+ K_subs]) of several library variants on
 one config in ONE process (the samples are generated once), round-robin so
 that drift hits every variant alike; HIP events, median per variant.
-  KEXP_CFG=c2 [KEXP_ROUNDS=3] [KEXP_REPS=10] python3 scripts/kp_multi.py a.so b.so ..."""
+  KEXP_CFG=c2 [KEXP_ROUNDS=3] [KEXP_REPS=10] [KEXP_PARSE_CUS=192] python3 scripts/kp_multi.py a.so b.so ...
+KEXP_PARSE_CUS: the CUs the parse grid is sized for (0: all), as bench.py sets it with batches in flight."""
 import importlib
 import os
 import sys
@@ -23,7 +24,8 @@ libs = [os.path.abspath(p) for p in sys.argv[1:]]
 eng.LIB_PATH = libs[0]
 eng.lib()  # the first variant loads the HIP runtime the same way the product does
 samples, _ = bench.shard_samples(pkg, cfg, 0, 1)
-batch = eng.Batch(samples)
+parse_cus = int(os.environ.get("KEXP_PARSE_CUS", "0"))
+batch = eng.Batch(samples, parse_cus=parse_cus)
 st = torch.cuda.current_stream()
 times = {p: [] for p in libs}
 for r in range(rounds):
@@ -51,5 +53,5 @@ for r in range(rounds):
         del plan
 for p in libs:
     t = times[p]
-    print("%s %s %.1f us (rounds: %s)" % (cfg, os.path.basename(p), float(np.median(t)), " ".join("%.1f" % x for x in t)),
+    print("%s parse_cus %d %s %.1f us (rounds: %s)" % (cfg, parse_cus, os.path.basename(p), float(np.median(t)), " ".join("%.1f" % x for x in t)),
           flush=True)

@@ -5,7 +5,8 @@ bench.py workload.  Read the SHARES, not the totals: the stamps' own
 lgkmcnt(0) waits forbid overlaps the product kernel has.
 
   hipcc ... -DMPC_STAMPS -o build/variants/stamps.so   (scripts/build_variants.sh stamps=-DMPC_STAMPS)
-  python3 scripts/kparse_stamps.py build/variants/stamps.so c2 [c3 ...]
+  [KEXP_PARSE_CUS=192] python3 scripts/kparse_stamps.py build/variants/stamps.so c2 [c3 ...]
+KEXP_PARSE_CUS: the CUs the parse grid is sized for (0: all), as bench.py sets it with batches in flight.
 """
 import ctypes
 import importlib
@@ -36,7 +37,7 @@ def main():
     out = {}
     for cfg in cfgs:
         samples, _ = bench.shard_samples(pkg, cfg, 0, 1)
-        plan = eng.Plan(eng.Batch(samples))
+        plan = eng.Plan(eng.Batch(samples, parse_cus=int(os.environ.get("KEXP_PARSE_CUS", "0"))))
         for _ in range(3):
             plan.phase("parse")
         torch.cuda.synchronize()
