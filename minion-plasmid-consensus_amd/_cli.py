@@ -98,8 +98,8 @@ def verdict_exit(label, strict, verdict):
     return 2 if strict and verdict == "FAIL" else 0
 
 
-def key_value_report(keys, rows_of_values, verdict):
+def key_value_report(keys, rows_of_values, verdict, verdict_key="verdict"):
     """One 'key<TAB>value' line per key for every row of values, then the verdict line."""
     out = ["{}\t{}\n".format(k, v) for values in rows_of_values for k, v in zip(keys, values)]
-    out.append("verdict\t{}\n".format(verdict))
+    out.append("{}\t{}\n".format(verdict_key, verdict))
     return "".join(out)

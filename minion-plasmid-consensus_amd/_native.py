@@ -22,7 +22,7 @@ _LAST_ERROR = (cp, [])
 
 
 def device_prototypes():
-    """libmpc.so: mpc.h and the device halves of the four tool headers."""
+    """libmpc.so: mpc.h and the device halves of the five tool headers."""
     from .engine import PHASES, PlanInfo, _Input
     table = {
         "mpc_version": (i32, []), "mpc_build_flags": (i32, []), "mpc_last_error": _LAST_ERROR,
@@ -47,13 +47,15 @@ def device_prototypes():
         "mpc_linkage_scratch_bytes": (i64, [i64, i32]),
         "mpc_align_revcomp": (i32, [vp, i64, vp, i32, vp]),
         "mpc_align_trace": (i32, [vp, i64, vp, i32, vp, i64, vp, vp, i64, vp]),
+        "mpc_draft_vote": (i32, [vp, i64, vp, i32, vp, vp, i64, vp, i64, vp, vp]),
+        "mpc_draft_call": (i32, [vp, vp, i64, vp, i64, vp, vp, vp]),
     }
     table.update(("mpc_" + phase, (i32, [vp, vp])) for phase in PHASES)
     return table
 
 
 def host_prototypes():
-    """libmpc_ingest.so: mpc_ingest.h and the host halves of the four tool headers."""
+    """libmpc_ingest.so: mpc_ingest.h and the host halves of the five tool headers."""
     from .coverage import _Paf
     from .ingest import _IngestOut
     from .pseudopair_reads import _Stats
@@ -80,6 +82,9 @@ def host_prototypes():
         "mpc_align_trace_host": (i32, [vp, i64, vp, i32, vp, vp, i64, i32]),
         "mpc_align_render": (i32, [vp, i64, vp, i32, vp, vp, vp, i64, vp, vp, cp, vp, i64, vp, P(i64), i32]),
         "mpc_align_last_error": _LAST_ERROR,
+        "mpc_draft_vote_host": (i32, [vp, i64, vp, i32, vp, vp, i64, vp, i64, vp, i32]),
+        "mpc_draft_call_host": (i32, [vp, vp, i64, vp, i64, vp]),
+        "mpc_draft_last_error": _LAST_ERROR,
     }
 
 

@@ -190,12 +190,14 @@ def jobs_of(pk, pl, reads):
     return jobs
 
 
-def trace(seq, jobs, device=0, threads=0, d_seq=None, workspace=None):
+def trace(seq, jobs, device=0, threads=0, d_seq=None, workspace=None, device_tensors=None):
     """(rc, out int32 [J, 8], runs int32[]) of one launch: mpc_align_trace on a
     GPU, mpc_align_trace_host for device="cpu".  rc is 0 or E_SCAN (a read's
     band did not give its scan distance; out holds the statuses); any other
     failure raises.  ``d_seq``: the blob's device copy when there is one;
-    ``workspace``: a dict that keeps the flag workspace between launches."""
+    ``workspace``: a dict that keeps the flag workspace between launches;
+    ``device_tensors``: a dict that receives the launch's device tensors (seq,
+    jobs, out, runs) for a step that goes on with them there (draft.vote)."""
     jobs = np.ascontiguousarray(jobs, np.int64).reshape(-1, 8)
     J = len(jobs)
     runs_cap = int((jobs[:, 7] + 2 * jobs[:, 4] + 1).max()) if J else 0
@@ -232,6 +234,8 @@ def trace(seq, jobs, device=0, threads=0, d_seq=None, workspace=None):
             engine._check(rc)
         out = d_out.cpu().numpy().reshape(J, 8)
         runs = d_runs.cpu().numpy()
+        if device_tensors is not None:
+            device_tensors.update(seq=d_seq, jobs=d_jobs, out=d_out, runs=d_runs)
     return rc, out, runs[:runs_cap]
 
 

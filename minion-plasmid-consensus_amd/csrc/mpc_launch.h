@@ -1,5 +1,5 @@
-// mpc_launch.h -- what the launchers of the four tool .hip files (mpc_verify,
-// mpc_cov, mpc_link, mpc_align) share on the host side of a launch: the error
+// mpc_launch.h -- what the launchers of the five tool .hip files (mpc_verify,
+// mpc_cov, mpc_link, mpc_align, mpc_draft) share on the host side of a launch: the error
 // message of libmpc.so, the read-back of device tables the host checks before
 // it launches, and the record grid of the two cs walks.
 #pragma once
