@@ -8,12 +8,16 @@ device plumbing the tools share.
                  ingest._native: they keep the path, the build and the
                  HIP-runtime rules)
   host           libmpc_ingest.so or the caller's error
-  device         (torch, torch.device) with libmpc.so loaded first
-  stream_ptr     the current stream of a device as the C-ABI takes it
+  host_check     a host call's return code, or the tool's error with its last_error
+  Device         the scope of a call into libmpc.so on one GPU: torch, dev, lib,
+                 stream, the H2D copies (put, put_all) and the check of its
+                 return code
 
 libmpc_synth.so has no public header: synth.py binds it.
 """
 import ctypes
+
+import numpy as np
 
 P = ctypes.POINTER
 vp, cp, dbl, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_size_t
@@ -109,16 +113,59 @@ def host(err):
     return L
 
 
-def device(device, cpu_path="host walk"):
-    """(torch, torch.device) of a GPU.  libmpc.so is loaded before torch is
-    imported: one HIP runtime in the process."""
-    from . import engine
-    engine.lib()
-    import torch
-    if not torch.cuda.is_available():
-        raise engine.MpcError("no HIP device visible (use device='cpu' for the {})".format(cpu_path))
-    return torch, torch.device("cuda", int(device))
+def host_check(L, tool, err, rc, accept=()):
+    """rc of a host call of ``tool`` when it is 0 or in ``accept``; else err with
+    the text of mpc_<tool>_last_error."""
+    if rc != 0 and rc not in accept:
+        raise err(getattr(L, "mpc_{}_last_error".format(tool))().decode(errors="replace"))
+    return rc
 
 
-def stream_ptr(torch, dev):
-    return vp(torch.cuda.current_stream(dev).cuda_stream)
+class Device:
+    """A call into libmpc.so on GPU ``device``: torch, dev, lib and, once
+    entered (torch.cuda.device(dev)), stream: the current stream as the C-ABI
+    takes it.  libmpc.so is loaded before torch is imported: one HIP runtime in
+    the process."""
+
+    def __init__(self, device, cpu_path="host path"):
+        from . import engine
+        self.lib = engine.lib()
+        import torch
+        if not torch.cuda.is_available():
+            raise engine.MpcError("no HIP device visible (use device='cpu' for the {})".format(cpu_path))
+        self.torch, self.dev, self._error = torch, torch.device("cuda", int(device)), engine.MpcError
+
+    def __enter__(self):
+        self._guard = self.torch.cuda.device(self.dev)
+        self._guard.__enter__()
+        self.stream = vp(self.torch.cuda.current_stream(self.dev).cuda_stream)
+        return self
+
+    def __exit__(self, *exc):
+        return self._guard.__exit__(*exc)
+
+    def put(self, a):
+        """The bytes of a numpy array as a uint8 tensor on the device."""
+        a = np.ascontiguousarray(a)
+        d = self.torch.empty(a.nbytes, dtype=self.torch.uint8, device=self.dev)
+        if a.nbytes:
+            d.copy_(self.torch.from_numpy(a.reshape(-1).view(np.uint8)))
+        return d
+
+    def put_all(self, parts):
+        """Device pointers of the numpy arrays ``parts``, and the tensor that owns
+        them: one blob, one H2D copy (int64 tables first keeps them 8-byte
+        aligned), 8 spare bytes behind the last part."""
+        parts = list(parts) + [np.zeros(8, np.uint8)]
+        offs = np.cumsum([0] + [p.nbytes for p in parts])
+        d_blob = self.put(np.concatenate([p.view(np.uint8).reshape(-1) for p in parts]))
+        return [d_blob.data_ptr() + int(o) for o in offs[:-2]], d_blob
+
+    def check(self, rc, accept=(), refused=None):
+        """rc when it is 0 or in ``accept``.  -1 (MPC_E_ARG: the tables were
+        refused before any launch) raises ``refused``, when given, with the text
+        of mpc_last_error; every other code raises MpcError."""
+        if rc == 0 or rc in accept:
+            return rc
+        text = self.lib.mpc_last_error().decode(errors="replace")
+        raise refused(text) if refused is not None and rc == -1 else self._error(f"libmpc error {rc}: {text}")

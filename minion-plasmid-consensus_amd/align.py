@@ -21,7 +21,6 @@ import ctypes
 import numpy as np
 
 from . import _native, verify
-from .verify import _to_device
 
 MAX_QUERY = 65536                 # mpc_verify.h MPC_VERIFY_MAX_QUERY
 MAX_EDITS = 4096                  # mpc_align.h MPC_ALIGN_MAX_EDITS
@@ -33,6 +32,15 @@ SUMMARY_FIELDS = ("reads", "mapped", "plus", "minus", "unmapped_by_distance", "u
 
 class AlignError(ValueError):
     """Input that cannot be aligned (the CLI exits 1)."""
+
+
+class TraceError(AlignError):
+    """The band DP of a read does not reproduce its scan distance: ``read`` is
+    its index among the batch's reads, ``status`` what the trace says of it."""
+
+    def __init__(self, read, status):
+        super().__init__("read {}: the band DP does not reproduce the scan's distance".format(read))
+        self.read, self.status = read, status
 
 
 # ---- FASTA ---------------------------------------------------------------------
@@ -94,11 +102,8 @@ def host_lib():
     return _native.host(AlignError)
 
 
-def _host_error(L):
-    return L.mpc_align_last_error().decode(errors="replace")
-
-
-device_lib = verify.device_lib
+def _host_check(L, rc, accept=()):
+    return _native.host_check(L, "align", AlignError, rc, accept)
 
 
 # ---- the steps, one batch at a time --------------------------------------------
@@ -143,17 +148,12 @@ def orient_and_scan(pk, device=0, threads=0):
     rc_tab = pk.revcomp_table()
     if device == "cpu":
         L = host_lib()
-        if L.mpc_align_revcomp_host(pk.seq.ctypes.data, pk.seq.nbytes, rc_tab.ctypes.data, R, threads) != 0:
-            raise AlignError(_host_error(L))
+        _host_check(L, L.mpc_align_revcomp_host(pk.seq.ctypes.data, pk.seq.nbytes, rc_tab.ctypes.data, R, threads))
     else:
-        from . import engine
-        torch, dev = _native.device(device, "host path")
-        L = device_lib()
-        with torch.cuda.device(dev):
-            stream = _native.stream_ptr(torch, dev)
-            pk.d_seq = _to_device(torch, dev, pk.seq)
-            d_tab = _to_device(torch, dev, rc_tab)
-            engine._check(L.mpc_align_revcomp(pk.d_seq.data_ptr(), pk.seq.nbytes, d_tab.data_ptr(), R, stream))
+        with _native.Device(device) as d:
+            pk.d_seq = d.put(pk.seq)
+            d_tab = d.put(rc_tab)
+            d.check(d.lib.mpc_align_revcomp(pk.d_seq.data_ptr(), pk.seq.nbytes, d_tab.data_ptr(), R, d.stream))
             a, b = pk.minus_span
             pk.seq[a:b] = pk.d_seq[a:b].cpu().numpy()  # the renderer reads the oriented reads on the host
     try:
@@ -173,9 +173,8 @@ def plan(scan, lens, max_error=0.2, workspace_bytes=DEFAULT_WORKSPACE):
     out = np.zeros((R, 8), np.int64)
     cuts = np.zeros(R + 1, np.int32)
     nl = ctypes.c_int32(0)
-    if L.mpc_align_plan(scan.ctypes.data, lens32.ctypes.data, R, float(max_error), int(workspace_bytes), out.ctypes.data,
-                        cuts.ctypes.data, ctypes.byref(nl)) != 0:
-        raise AlignError(_host_error(L))
+    _host_check(L, L.mpc_align_plan(scan.ctypes.data, lens32.ctypes.data, R, float(max_error), int(workspace_bytes),
+                                    out.ctypes.data, cuts.ctypes.data, ctypes.byref(nl)))
     return out, [int(c) for c in cuts[:nl.value + 1]]
 
 
@@ -207,31 +206,25 @@ def trace(seq, jobs, device=0, threads=0, d_seq=None, workspace=None, device_ten
         return 0, out, runs[:0]
     if device == "cpu":
         L = host_lib()
-        rc = L.mpc_align_trace_host(seq.ctypes.data, seq.nbytes, jobs.ctypes.data, J, out.ctypes.data, runs.ctypes.data,
-                                    runs_cap, threads)
-        if rc not in (0, E_SCAN):
-            raise AlignError(_host_error(L))
+        rc = _host_check(L, L.mpc_align_trace_host(seq.ctypes.data, seq.nbytes, jobs.ctypes.data, J, out.ctypes.data,
+                                                   runs.ctypes.data, runs_cap, threads), accept=(E_SCAN,))
         return rc, out, runs[:runs_cap]
-    from . import engine
-    torch, dev = _native.device(device, "host path")
-    L = device_lib()
     pitch = (2 * jobs[:, 4] + 1 + 63) // 64 * 64
     flags_bytes = max(int((jobs[:, 6] + jobs[:, 1] * pitch).max()), 64)
-    with torch.cuda.device(dev):
-        stream = _native.stream_ptr(torch, dev)
+    with _native.Device(device) as d:
+        torch, dev = d.torch, d.dev
         if d_seq is None:
-            d_seq = _to_device(torch, dev, seq)
+            d_seq = d.put(seq)
         ws = workspace if workspace is not None else {}
         if ws.get("flags") is None or ws["flags"].numel() < flags_bytes or ws["flags"].device != dev:
             ws["flags"] = None  # (free before growing)
             ws["flags"] = torch.empty(flags_bytes, dtype=torch.uint8, device=dev)
-        d_jobs = _to_device(torch, dev, jobs)
+        d_jobs = d.put(jobs)
         d_out = torch.zeros(8 * J, dtype=torch.int32, device=dev)
         d_runs = torch.zeros(max(runs_cap, 1), dtype=torch.int32, device=dev)
-        rc = L.mpc_align_trace(d_seq.data_ptr(), seq.nbytes, d_jobs.data_ptr(), J, ws["flags"].data_ptr(),
-                               ws["flags"].numel(), d_out.data_ptr(), d_runs.data_ptr(), runs_cap, stream)
-        if rc not in (0, E_SCAN):
-            engine._check(rc)
+        rc = d.check(d.lib.mpc_align_trace(d_seq.data_ptr(), seq.nbytes, d_jobs.data_ptr(), J, ws["flags"].data_ptr(),
+                                           ws["flags"].numel(), d_out.data_ptr(), d_runs.data_ptr(), runs_cap, d.stream),
+                     accept=(E_SCAN,))
         out = d_out.cpu().numpy().reshape(J, 8)
         runs = d_runs.cpu().numpy()
         if device_tensors is not None:
@@ -256,11 +249,42 @@ def render(seq, jobs, strand, out, runs, names, tname, threads=0):
     buf = ctypes.create_string_buffer(cap)
     line_len = np.zeros(J, np.int64)
     written = ctypes.c_int64(0)
-    if L.mpc_align_render(seq.ctypes.data, seq.nbytes, jobs.ctypes.data, J, strand.ctypes.data, out.ctypes.data,
-                          runs.ctypes.data, len(runs), blob, name_off.ctypes.data, tname, ctypes.addressof(buf), cap,
-                          line_len.ctypes.data, ctypes.byref(written), threads) != 0:
-        raise AlignError(_host_error(L))
+    _host_check(L, L.mpc_align_render(seq.ctypes.data, seq.nbytes, jobs.ctypes.data, J, strand.ctypes.data, out.ctypes.data,
+                                      runs.ctypes.data, len(runs), blob, name_off.ctypes.data, tname, ctypes.addressof(buf),
+                                      cap, line_len.ctypes.data, ctypes.byref(written), threads))
     return buf.raw[:written.value], line_len
+
+
+class Launches:
+    """The reads of one batch against a target, scanned and planned (pk, scan,
+    plan, cuts); iterating traces launch after launch of the plan's cut and
+    gives (reads, jobs, out, runs, device tensors) of each, an empty one too:
+    the indices of its mapped reads, their job table and what trace returns.
+    ``workspace``: the dict that keeps the flag workspace between launches and
+    batches; ``keep_device``: hand on each launch's device tensors (else, and
+    for device="cpu", None).  A read whose band does not give its scan
+    distance raises TraceError.  pk.d_seq stays until the caller drops it."""
+
+    def __init__(self, target, reads, device=0, max_error=0.2, workspace_bytes=DEFAULT_WORKSPACE, threads=0,
+                 workspace=None, keep_device=False):
+        self.device, self.threads, self.keep_device = device, threads, keep_device
+        self.workspace = workspace if workspace is not None else {}
+        self.pk = Packed(target, reads)
+        self.scan = orient_and_scan(self.pk, device, threads)
+        self.plan, self.cuts = plan(self.scan, self.pk.lens, max_error, workspace_bytes)
+
+    def __iter__(self):
+        pk, pl = self.pk, self.plan
+        for a, b in zip(self.cuts[:-1], self.cuts[1:]):
+            reads = [r for r in range(a, b) if pl[r, 1]]
+            jobs = jobs_of(pk, pl, reads)
+            kept = {} if self.keep_device else None
+            rc, out, runs = trace(pk.seq, jobs, self.device, self.threads, d_seq=pk.d_seq, workspace=self.workspace,
+                                  device_tensors=kept)
+            if rc != 0:
+                k = int(np.nonzero(out[:, 0])[0][0])
+                raise TraceError(reads[k], int(out[k, 0]))
+            yield reads, jobs, out, runs, kept or None
 
 
 def align_records(target, tname, records, device=0, max_error=0.2, workspace_bytes=DEFAULT_WORKSPACE, threads=0,
@@ -273,34 +297,29 @@ def align_records(target, tname, records, device=0, max_error=0.2, workspace_byt
     keep = [k for k, (_, s) in enumerate(records) if 1 <= len(s) <= MAX_QUERY]
     counts["skipped_length"] = len(records) - len(keep)
     names = [records[k][0] for k in keep]
-    pk = Packed(target, [records[k][1] for k in keep])
-    scan = orient_and_scan(pk, device, threads)
-    pl, cuts = plan(scan, pk.lens, max_error, workspace_bytes)
+    loop = Launches(target, [records[k][1] for k in keep], device, max_error, workspace_bytes, threads, workspace)
+    pk, pl = loop.pk, loop.plan
     counts["unmapped_by_distance"] = int((pl[:, 1] == 0).sum()) if len(keep) else 0
-    ws = workspace if workspace is not None else {}
-    parts, det = [], dict(kept=keep, scan=scan, plan=pl, cuts=cuts, out={}, runs={})
-    for a, b in zip(cuts[:-1], cuts[1:]):
-        reads = [r for r in range(a, b) if pl[r, 1]]
-        jobs = jobs_of(pk, pl, reads)
-        rc, out, runs = trace(pk.seq, jobs, device, threads, d_seq=pk.d_seq, workspace=ws)
-        if rc != 0:
-            bad = [reads[k] for k in np.nonzero(out[:, 0])[0]]
-            raise AlignError("read {!r}: the band DP does not reproduce the scan's distance (status {})".format(
-                names[bad[0]].decode(errors="replace"), int(out[np.nonzero(out[:, 0])[0][0], 0])))
-        text, line_len = render(pk.seq, jobs, pl[reads, 0], out, runs, [names[r] for r in reads], tname, threads)
-        parts.append(text)
-        wrote = line_len > 0
-        minus = pl[reads, 0] != 0
-        counts["mapped"] += int(wrote.sum())
-        counts["minus"] += int((wrote & minus).sum())
-        counts["plus"] += int((wrote & ~minus).sum())
-        counts["unmapped_no_match"] += int((~wrote).sum())
-        if detail:
-            for k, r in enumerate(reads):
-                det["out"][r] = out[k].copy()
-                det["runs"][r] = runs[jobs[k, 7]: jobs[k, 7] + out[k, 6]].copy()
+    parts, det = [], dict(kept=keep, scan=loop.scan, plan=pl, cuts=loop.cuts, out={}, runs={})
+    try:
+        for reads, jobs, out, runs, _ in loop:
+            text, line_len = render(pk.seq, jobs, pl[reads, 0], out, runs, [names[r] for r in reads], tname, threads)
+            parts.append(text)
+            wrote = line_len > 0
+            minus = pl[reads, 0] != 0
+            counts["mapped"] += int(wrote.sum())
+            counts["minus"] += int((wrote & minus).sum())
+            counts["plus"] += int((wrote & ~minus).sum())
+            counts["unmapped_no_match"] += int((~wrote).sum())
+            if detail:
+                for k, r in enumerate(reads):
+                    det["out"][r] = out[k].copy()
+                    det["runs"][r] = runs[jobs[k, 7]: jobs[k, 7] + out[k, 6]].copy()
+    except TraceError as e:
+        raise AlignError("read {!r}: the band DP does not reproduce the scan's distance (status {})".format(
+            names[e.read].decode(errors="replace"), e.status))
     pk.d_seq = None
-    res = dict(paf=b"".join(parts), counts=counts, launches=len(cuts) - 1)
+    res = dict(paf=b"".join(parts), counts=counts, launches=len(loop.cuts) - 1)
     if detail:
         res["detail"] = det
     return res

@@ -51,15 +51,10 @@ def host_lib():
     return _native.host(CoverageError)
 
 
-def _device_lib():
-    """libmpc.so (its prototypes: _native.device_prototypes)."""
-    from . import engine
-    return engine.lib()
-
-
 def tile_bytes():
     """cs bytes K_covparse takes per tile (no GPU needed)."""
-    return _device_lib().mpc_coverage_tile_bytes()
+    from . import engine
+    return engine.lib().mpc_coverage_tile_bytes()
 
 
 def _copy(ptr, n, dtype):
@@ -119,18 +114,6 @@ def batch_front(err, cs, cs_off, tstart, rec_sample, lengths, more=()):
     return cs, cs_off, tstart, rec_sample, pos_off
 
 
-def upload(torch, dev, parts):
-    """Device pointers of the numpy arrays `parts`, and the tensor that owns
-    them: one blob, one H2D copy (int64 tables first keeps them 8-byte aligned),
-    8 spare bytes behind the last part."""
-    parts = list(parts) + [np.zeros(8, np.uint8)]
-    offs = np.cumsum([0] + [p.nbytes for p in parts])
-    blob = np.concatenate([p.view(np.uint8).reshape(-1) for p in parts])
-    d_blob = torch.empty(len(blob), dtype=torch.uint8, device=dev)
-    d_blob.copy_(torch.from_numpy(blob))
-    return [d_blob.data_ptr() + int(o) for o in offs[:-2]], d_blob
-
-
 def raise_status(err, status):
     """The C-ABI's status {code, smallest offending record} as err, if any."""
     if status[0] != 0:
@@ -159,22 +142,20 @@ def run(cs, cs_off, tstart, rec_sample, lengths, regions=None, min_depth=0, devi
         stats = np.zeros((S, STATS), np.uint64)
         status = np.zeros(2, np.int32)
         rec_out = np.zeros((n, 2), np.int64)
-        if L.mpc_coverage_host(cs.ctypes.data, cs_off.ctypes.data, tstart.ctypes.data, rec_sample.ctypes.data, n,
-                               pos_off.ctypes.data, region.ctypes.data, S, min_depth, rows.ctypes.data,
-                               stats.ctypes.data, status.ctypes.data, threads, rec_out.ctypes.data) != 0:
-            raise CoverageError(L.mpc_coverage_last_error().decode(errors="replace"))
+        _native.host_check(L, "coverage", CoverageError, L.mpc_coverage_host(
+            cs.ctypes.data, cs_off.ctypes.data, tstart.ctypes.data, rec_sample.ctypes.data, n, pos_off.ctypes.data,
+            region.ctypes.data, S, min_depth, rows.ctypes.data, stats.ctypes.data, status.ctypes.data, threads,
+            rec_out.ctypes.data))
     else:
-        from . import engine
-        torch, dev = _native.device(device)
-        with torch.cuda.device(dev):
+        with _native.Device(device, "host walk") as d:
+            torch, dev = d.torch, d.dev
             # the int64 tables first, then rec_sample, then the cs bytes
-            at, d_blob = upload(torch, dev, [cs_off, tstart, pos_off, region.reshape(-1), rec_sample, cs])
+            at, d_blob = d.put_all([cs_off, tstart, pos_off, region.reshape(-1), rec_sample, cs])
             d_rows = torch.empty((n_pos, 4), dtype=torch.int32, device=dev)
             d_stats = torch.empty((S, STATS), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            engine._check(engine.lib().mpc_coverage_run(at[5], at[0], at[1], at[4], n, at[2], at[3], S, min_depth,
-                                                        d_rows.data_ptr(), d_stats.data_ptr(), d_status.data_ptr(),
-                                                        _native.stream_ptr(torch, dev)))
+            d.check(d.lib.mpc_coverage_run(at[5], at[0], at[1], at[4], n, at[2], at[3], S, min_depth, d_rows.data_ptr(),
+                                           d_stats.data_ptr(), d_status.data_ptr(), d.stream))
             status = d_status.cpu().numpy()
             rows = d_rows.cpu().numpy().view(np.uint32)
             stats = d_stats.cpu().numpy().view(np.uint64)

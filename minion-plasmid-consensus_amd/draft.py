@@ -19,7 +19,6 @@ import math
 import numpy as np
 
 from . import _native, align
-from .verify import _to_device
 
 ROW = 48                # mpc_draft.h MPC_DRAFT_ROW
 SLOTS = 8               # mpc_draft.h MPC_DRAFT_SLOTS
@@ -38,13 +37,6 @@ def host_lib():
     return _native.host(DraftError)
 
 
-def _host_error(L):
-    return L.mpc_draft_last_error().decode(errors="replace")
-
-
-device_lib = align.device_lib
-
-
 # ---- vote and call, one launch at a time ----------------------------------------
 
 def new_tally(n, device=0):
@@ -52,8 +44,8 @@ def new_tally(n, device=0):
     device="cpu", else a flat int32 torch tensor on that GPU)."""
     if device == "cpu":
         return np.zeros((n + 1, ROW), np.uint32)
-    torch, dev = _native.device(device, "host path")
-    return torch.zeros((n + 1) * ROW, dtype=torch.int32, device=dev)
+    d = _native.Device(device)
+    return d.torch.zeros((n + 1) * ROW, dtype=d.torch.int32, device=d.dev)
 
 
 def tally_to_host(tally):
@@ -78,25 +70,18 @@ def vote(tally, n, seq, jobs, out, runs, device=0, threads=0, device_tensors=Non
         runs = np.ascontiguousarray(runs, np.int32)
         rc = L.mpc_draft_vote_host(seq.ctypes.data, seq.nbytes, jobs.ctypes.data, J, out.ctypes.data, runs.ctypes.data,
                                    len(runs), tally.ctypes.data, n, status.ctypes.data, threads)
-        if rc not in (0, E_RUNS):
-            raise DraftError(_host_error(L))
-        return rc, status
-    from . import engine
-    torch, dev = _native.device(device, "host path")
-    L = device_lib()
-    with torch.cuda.device(dev):
+        return _native.host_check(L, "draft", DraftError, rc, accept=(E_RUNS,)), status
+    with _native.Device(device) as d:
         t = device_tensors or {}
-        d_seq = t["seq"] if "seq" in t else _to_device(torch, dev, seq)
-        d_jobs = t["jobs"] if "jobs" in t else _to_device(torch, dev, jobs)
-        d_out = t["out"] if "out" in t else _to_device(torch, dev, np.ascontiguousarray(out, np.int32))
-        d_runs = t["runs"] if "runs" in t else _to_device(torch, dev, np.ascontiguousarray(runs, np.int32))
+        d_seq = t["seq"] if "seq" in t else d.put(seq)
+        d_jobs = t["jobs"] if "jobs" in t else d.put(jobs)
+        d_out = t["out"] if "out" in t else d.put(np.ascontiguousarray(out, np.int32))
+        d_runs = t["runs"] if "runs" in t else d.put(np.ascontiguousarray(runs, np.int32))
         runs_cap = d_runs.numel() * d_runs.element_size() // 4
-        d_status = torch.zeros(J, dtype=torch.int32, device=dev)
-        rc = L.mpc_draft_vote(d_seq.data_ptr(), d_seq.numel(), d_jobs.data_ptr(), J, d_out.data_ptr(), d_runs.data_ptr(),
-                              runs_cap, tally.data_ptr(), n, d_status.data_ptr(), _native.stream_ptr(torch, dev))
-        if rc not in (0, E_RUNS):
-            engine._check(rc)
-        return rc, d_status.cpu().numpy()
+        d_status = d.torch.zeros(J, dtype=d.torch.int32, device=d.dev)
+        rc = d.lib.mpc_draft_vote(d_seq.data_ptr(), d_seq.numel(), d_jobs.data_ptr(), J, d_out.data_ptr(), d_runs.data_ptr(),
+                                  runs_cap, tally.data_ptr(), n, d_status.data_ptr(), d.stream)
+        return d.check(rc, accept=(E_RUNS,)), d_status.cpu().numpy()
 
 
 def call(tally, draft, device=0, d_draft=None):
@@ -109,24 +94,21 @@ def call(tally, draft, device=0, d_draft=None):
         L = host_lib()
         new = np.zeros(cap, np.uint8)
         info = np.zeros(8, np.int32)
-        d = np.frombuffer(draft, np.uint8)
-        if L.mpc_draft_call_host(tally.ctypes.data, d.ctypes.data, n, new.ctypes.data, cap, info.ctypes.data) != 0:
-            raise DraftError(_host_error(L))
+        h = np.frombuffer(draft, np.uint8)
+        _native.host_check(L, "draft", DraftError,
+                           L.mpc_draft_call_host(tally.ctypes.data, h.ctypes.data, n, new.ctypes.data, cap, info.ctypes.data))
     else:
-        from . import engine
-        torch, dev = _native.device(device, "host path")
-        L = device_lib()
-        with torch.cuda.device(dev):
+        with _native.Device(device) as d:
+            torch, dev = d.torch, d.dev
             if d_draft is None:
-                d_draft = _to_device(torch, dev, np.frombuffer(draft, np.uint8).copy())  # (writable: torch takes no read-only array)
+                d_draft = d.put(np.frombuffer(draft, np.uint8).copy())  # (writable: torch takes no read-only array)
             d_new = torch.zeros(cap, dtype=torch.uint8, device=dev)
             d_work = torch.empty(3 * (n + 1), dtype=torch.int32, device=dev)
             d_info = torch.zeros(8, dtype=torch.int32, device=dev)
-            rc = L.mpc_draft_call(tally.data_ptr(), d_draft.data_ptr(), n, d_new.data_ptr(), cap, d_work.data_ptr(),
-                                  d_info.data_ptr(), _native.stream_ptr(torch, dev))
-            if rc in (E_EMPTY, E_LONG):
-                raise DraftError(L.mpc_last_error().decode(errors="replace"))
-            engine._check(rc)
+            rc = d.lib.mpc_draft_call(tally.data_ptr(), d_draft.data_ptr(), n, d_new.data_ptr(), cap, d_work.data_ptr(),
+                                      d_info.data_ptr(), d.stream)
+            if d.check(rc, accept=(E_EMPTY, E_LONG)) != 0:  # (no read mapped, or a draft above MAX_LEN: the input's fault)
+                raise DraftError(d.lib.mpc_last_error().decode(errors="replace"))
             info = d_info.cpu().numpy()
             new = d_new[:int(info[1])].cpu().numpy()
     info = dict(zip(INFO_FIELDS, (int(v) for v in info)))
@@ -176,32 +158,27 @@ def pick_seed(records, candidates=8, max_error=0.3, device=0, threads=0):
 
 def polish_round(draft, reads, device=0, max_error=0.3, workspace_bytes=align.DEFAULT_WORKSPACE, threads=0, workspace=None):
     """One round: (new draft, info) with info["mapped"] = reads voted and
-    info["launches"].  The sample is aligned exactly as align.align_records does it."""
+    info["launches"].  The sample is aligned by align.Launches, as align.align_records does it."""
     n = len(draft)
     if not 1 <= n <= MAX_LEN:
         raise DraftError("a draft of {} bases (1 .. {} supported)".format(n, MAX_LEN))
-    pk = align.Packed(draft, reads)
-    scan = align.orient_and_scan(pk, device, threads)
-    pl, cuts = align.plan(scan, pk.lens, max_error, workspace_bytes)
-    ws = workspace if workspace is not None else {}
+    loop = align.Launches(draft, reads, device, max_error, workspace_bytes, threads, workspace, keep_device=True)
+    pk = loop.pk
     tally = new_tally(n, device)
     voted = 0
-    for a, b in zip(cuts[:-1], cuts[1:]):
-        rd = [r for r in range(a, b) if pl[r, 1]]
-        jobs = align.jobs_of(pk, pl, rd)
-        kept = {}
-        rc, out, runs = align.trace(pk.seq, jobs, device, threads, d_seq=pk.d_seq, workspace=ws, device_tensors=kept)
-        if rc != 0:
-            raise DraftError("read {}: the band DP does not reproduce the scan's distance".format(rd[int(np.nonzero(out[:, 0])[0][0])]))
-        rc, status = vote(tally, n, pk.seq, jobs, out, runs, device, threads, device_tensors=kept)
-        if rc != 0:
-            raise DraftError("read {}: its runs do not walk the read".format(rd[int(np.nonzero(status == BAD_RUNS)[0][0])]))
-        voted += int((status == VOTED).sum())
+    try:
+        for rd, jobs, out, runs, kept in loop:
+            rc, status = vote(tally, n, pk.seq, jobs, out, runs, device, threads, device_tensors=kept)
+            if rc != 0:
+                raise DraftError("read {}: its runs do not walk the read".format(rd[int(np.nonzero(status == BAD_RUNS)[0][0])]))
+            voted += int((status == VOTED).sum())
+    except align.TraceError as e:
+        raise DraftError(str(e))
     new, info = call(tally, draft, device, d_draft=pk.d_seq)
     pk.d_seq = None
     if not new:
         raise DraftError("the round dropped every column of the draft")
-    info.update(mapped=voted, launches=len(cuts) - 1)
+    info.update(mapped=voted, launches=len(loop.cuts) - 1)
     return new, info
 
 

@@ -46,7 +46,6 @@ def site_label(key):
 
 
 host_lib = coverage.host_lib
-_device_lib = engine.lib
 
 
 def tile_bytes():
@@ -56,12 +55,6 @@ def tile_bytes():
 
 def scratch_bytes(n_records, n_sites):
     return engine.lib().mpc_linkage_scratch_bytes(n_records, n_sites)
-
-
-def _device_check(L, rc):
-    if rc == -1:  # MPC_E_ARG: the tables were refused before any launch
-        raise LinkageError(L.mpc_last_error().decode(errors="replace"))
-    engine._check(rc)
 
 
 def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, threads=0):
@@ -81,23 +74,21 @@ def run(cs, cs_off, tstart, rec_sample, lengths, site_off, site_key, device=0, t
         alleles = np.zeros((n, K), np.uint8)
         pair = np.zeros((K, K, CODES, CODES), np.uint32)
         status = np.zeros(2, np.int32)
-        if L.mpc_linkage_host(cs.ctypes.data, cs_off.ctypes.data, tstart.ctypes.data, rec_sample.ctypes.data, n,
-                              pos_off.ctypes.data, S, site_off.ctypes.data, site_key.ctypes.data, K, alleles.ctypes.data,
-                              pair.ctypes.data, status.ctypes.data, threads) != 0:
-            raise LinkageError(L.mpc_linkage_last_error().decode(errors="replace"))
+        _native.host_check(L, "linkage", LinkageError, L.mpc_linkage_host(
+            cs.ctypes.data, cs_off.ctypes.data, tstart.ctypes.data, rec_sample.ctypes.data, n, pos_off.ctypes.data, S,
+            site_off.ctypes.data, site_key.ctypes.data, K, alleles.ctypes.data, pair.ctypes.data, status.ctypes.data, threads))
     else:
-        L = engine.lib()
-        torch, dev = _native.device(device)
-        with torch.cuda.device(dev):
+        with _native.Device(device, "host walk") as d:
+            torch, dev = d.torch, d.dev
             # the int64 tables first, then rec_sample, then the cs bytes
-            at, d_blob = coverage.upload(torch, dev, [cs_off, tstart, pos_off, site_off, site_key, rec_sample, cs])
+            at, d_blob = d.put_all([cs_off, tstart, pos_off, site_off, site_key, rec_sample, cs])
             d_alleles = torch.empty((n, K), dtype=torch.uint8, device=dev)
             d_pair = torch.empty((K, K, CODES, CODES), dtype=torch.int32, device=dev)
-            d_scratch = torch.empty(max(8, L.mpc_linkage_scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
+            d_scratch = torch.empty(max(8, scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            _device_check(L, L.mpc_linkage_run(at[6], at[0], at[1], at[5], n, at[2], S, at[3], at[4], K,
-                                               d_alleles.data_ptr(), d_pair.data_ptr(), d_scratch.data_ptr(),
-                                               d_status.data_ptr(), _native.stream_ptr(torch, dev)))
+            d.check(d.lib.mpc_linkage_run(at[6], at[0], at[1], at[5], n, at[2], S, at[3], at[4], K, d_alleles.data_ptr(),
+                                          d_pair.data_ptr(), d_scratch.data_ptr(), d_status.data_ptr(), d.stream),
+                    refused=LinkageError)
             status = d_status.cpu().numpy()
             alleles = d_alleles.cpu().numpy()
             pair = d_pair.cpu().numpy().view(np.uint32)
@@ -117,19 +108,18 @@ def pairs(alleles, device=0, threads=0):
     if device == "cpu":
         L = host_lib()
         pair = np.zeros((K, K, CODES, CODES), np.uint32)
-        if L.mpc_linkage_pairs_host(alleles.ctypes.data, n, K, pair.ctypes.data, threads) != 0:
-            raise LinkageError(L.mpc_linkage_last_error().decode(errors="replace"))
+        _native.host_check(L, "linkage", LinkageError,
+                           L.mpc_linkage_pairs_host(alleles.ctypes.data, n, K, pair.ctypes.data, threads))
         return pair
-    L = engine.lib()
-    torch, dev = _native.device(device)
-    with torch.cuda.device(dev):
+    with _native.Device(device, "host walk") as d:
+        torch, dev = d.torch, d.dev
         d_alleles = torch.empty((max(n, 1), K), dtype=torch.uint8, device=dev)
         if n:
             d_alleles[:n].copy_(torch.from_numpy(alleles))
         d_pair = torch.empty((K, K, CODES, CODES), dtype=torch.int32, device=dev)
-        d_scratch = torch.empty(max(8, L.mpc_linkage_scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
-        _device_check(L, L.mpc_linkage_pairs(d_alleles.data_ptr(), n, K, d_pair.data_ptr(), d_scratch.data_ptr(),
-                                             _native.stream_ptr(torch, dev)))
+        d_scratch = torch.empty(max(8, scratch_bytes(n, K) // 8), dtype=torch.int64, device=dev)
+        d.check(d.lib.mpc_linkage_pairs(d_alleles.data_ptr(), n, K, d_pair.data_ptr(), d_scratch.data_ptr(), d.stream),
+                refused=LinkageError)
         return d_pair.cpu().numpy().view(np.uint32)
 
 

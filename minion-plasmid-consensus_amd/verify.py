@@ -86,20 +86,6 @@ def _pack(pairs):
     return tab, seq
 
 
-def device_lib():
-    """libmpc.so (its prototypes: _native.device_prototypes)."""
-    from . import engine
-    return engine.lib()
-
-
-def _to_device(torch, dev, a):
-    a = np.ascontiguousarray(a)
-    d = torch.empty(a.nbytes, dtype=torch.uint8, device=dev)
-    if a.nbytes:
-        d.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8)))
-    return d
-
-
 def scan_table(seq, tab, device, threads=0, d_seq=None):
     """int32 [n, 2] = (distance, end) of the pairs of an int64 [n, 4] pair
     table {q_off, q_len, t_off, t_len} over the uint8 blob ``seq``:
@@ -113,19 +99,15 @@ def scan_table(seq, tab, device, threads=0, d_seq=None):
         return out
     if device == "cpu":
         L = host_lib()
-        if L.mpc_verify_scan_host(seq.ctypes.data, tab.ctypes.data, n, out.ctypes.data, threads) != 0:
-            raise VerifyError(L.mpc_verify_last_error().decode(errors="replace"))
+        _native.host_check(L, "verify", VerifyError,
+                           L.mpc_verify_scan_host(seq.ctypes.data, tab.ctypes.data, n, out.ctypes.data, threads))
         return out
-    from . import engine
-    torch, dev = _native.device(device, "host path")
-    L = device_lib()
-    with torch.cuda.device(dev):
+    with _native.Device(device) as d:
         if d_seq is None:
-            d_seq = _to_device(torch, dev, seq)
-        d_tab = _to_device(torch, dev, tab)
-        d_out = torch.empty(2 * n, dtype=torch.int32, device=dev)
-        engine._check(L.mpc_verify_scan(d_seq.data_ptr(), d_tab.data_ptr(), n, d_out.data_ptr(),
-                                        _native.stream_ptr(torch, dev)))
+            d_seq = d.put(seq)
+        d_tab = d.put(tab)
+        d_out = d.torch.empty(2 * n, dtype=d.torch.int32, device=d.dev)
+        d.check(d.lib.mpc_verify_scan(d_seq.data_ptr(), d_tab.data_ptr(), n, d_out.data_ptr(), d.stream))
         return d_out.cpu().numpy().reshape(n, 2)
 
 
@@ -151,8 +133,8 @@ def script(q, t, distance, end):
     start = ctypes.c_int32(-1)
     counts = (ctypes.c_int32 * 4)()
     buf = ctypes.create_string_buffer(_CIGAR_CAP)
-    if L.mpc_verify_script(q, len(q), t, len(t), distance, end, ctypes.byref(start), counts, buf, _CIGAR_CAP) != 0:
-        raise VerifyError(L.mpc_verify_last_error().decode(errors="replace"))
+    _native.host_check(L, "verify", VerifyError, L.mpc_verify_script(q, len(q), t, len(t), distance, end, ctypes.byref(start),
+                                                                     counts, buf, _CIGAR_CAP))
     return dict(start=start.value, matches=counts[0], mismatches=counts[1], insertions=counts[2],
                 deletions=counts[3], cigar=buf.value.decode("ascii"))
 

@@ -14,9 +14,6 @@ Prints one JSON line per batch; --out also writes them to a file.  The
 whole-tool wall times (align_records: pack, copies, plan, render included) of
 both devices are reported next to the kernels'."""
 import argparse
-import ctypes
-import importlib
-import json
 import os
 import statistics
 import sys
@@ -25,8 +22,7 @@ import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import _toolbench as tb
 
 
 def synth_batch(pkg, n, n_reads, seed):
@@ -38,94 +34,70 @@ def synth_batch(pkg, n, n_reads, seed):
         return tname, target, list(pkg.align.fasta_records(reads))
 
 
-def timed(torch, stream, launch, warmup, repeats):
-    for _ in range(warmup):
-        launch()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        launch()
-        e1.record(stream)
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return times
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", nargs="+", default=["2686:4096", "10000:512"], help="plasmid length:reads")
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--host-threads", type=int, default=16)
-    ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-error", type=float, default=0.2)
-    ap.add_argument("--out")
-    args = ap.parse_args()
+    args = tb.parse(ap, repeats=7, warmup=2)
 
-    pkg = importlib.import_module("minion-plasmid-consensus_amd")
-    al = pkg.align
-    L = al.device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("align_bench.py measures on a GPU; none is visible")
+    pkg, d = tb.gpu(args.device)
+    al, torch, dev = pkg.align, d.torch, d.dev
     H = al.host_lib()
-    dev = torch.device("cuda", args.device)
     results = []
     for spec in args.batches:
         n, n_reads = (int(x) for x in spec.split(":"))
         tname, target, records = synth_batch(pkg, n, n_reads, seed=300 + n_reads)
         reads = [s for _, s in records]
-        pk = al.Packed(target, reads)
-        R = len(reads)
-        pairs = pk.pair_table()
+        # the batch as the tool takes it (the device's reverse complements, scan and one traced launch):
+        # its blob, plan and job table are what both paths are then timed on
+        loop = al.Launches(target, reads, args.device, args.max_error, 8 << 30)
+        pk, pl, R = loop.pk, loop.plan, len(reads)
+        if len(loop.cuts) != 2:
+            sys.exit("the batch does not fit one launch under 8 GiB of flags: nothing to report")
+        (mapped, jobs, tool_out, tool_runs, _), = loop
+        pk.d_seq = None
+        loop.workspace.clear()
+        J = len(jobs)
+        pairs, rc_tab = pk.pair_table(), pk.revcomp_table()
         cells = int(2 * pk.n * pk.lens.sum())
 
-        # host: reverse complements, scan, plan, trace
-        rc_tab = pk.revcomp_table()
-        assert H.mpc_align_revcomp_host(pk.seq.ctypes.data, pk.seq.nbytes, rc_tab.ctypes.data, R, args.host_threads) == 0
+        # host: reverse complements, scan, trace
+        clean = pk.seq.copy()
+        clean[pk.minus_span[0]: pk.minus_span[1]] = 0
+        host_seq = clean.copy()
+        assert H.mpc_align_revcomp_host(host_seq.ctypes.data, host_seq.nbytes, rc_tab.ctypes.data, R, args.host_threads) == 0
         host_scan = np.zeros((R, 4), np.int32)
         t0 = time.perf_counter()
-        rc = H.mpc_verify_scan_host(pk.seq.ctypes.data, pairs.ctypes.data, 2 * R, host_scan.ctypes.data, args.host_threads)
+        rc = H.mpc_verify_scan_host(host_seq.ctypes.data, pairs.ctypes.data, 2 * R, host_scan.ctypes.data, args.host_threads)
         host_scan_s = time.perf_counter() - t0
         assert rc == 0
-        pl, cuts = al.plan(host_scan, pk.lens, args.max_error, 8 << 30)
-        if len(cuts) != 2:
-            sys.exit("the batch does not fit one launch under 8 GiB of flags: nothing to report")
-        mapped = [r for r in range(R) if pl[r, 1]]
-        jobs = al.jobs_of(pk, pl, mapped)
-        J = len(jobs)
         runs_cap = int((jobs[:, 7] + 2 * jobs[:, 4] + 1).max())
         flags_bytes = int((jobs[:, 6] + pl[mapped, 5]).max())
         host_out, host_runs = np.zeros((J, 8), np.int32), np.zeros(runs_cap, np.int32)
         t0 = time.perf_counter()
-        rc = H.mpc_align_trace_host(pk.seq.ctypes.data, pk.seq.nbytes, jobs.ctypes.data, J, host_out.ctypes.data,
+        rc = H.mpc_align_trace_host(host_seq.ctypes.data, host_seq.nbytes, jobs.ctypes.data, J, host_out.ctypes.data,
                                     host_runs.ctypes.data, runs_cap, args.host_threads)
         host_trace_s = time.perf_counter() - t0
         assert rc == 0
 
         # device: the same blob (its reverse complements made by K_arevcomp), the same tables
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            st = ctypes.c_void_p(stream.cuda_stream)
-            clean = pk.seq.copy()
-            clean[pk.minus_span[0]: pk.minus_span[1]] = 0
-            d_seq = al._to_device(torch, dev, clean)
-            d_tab, d_pairs, d_jobs = (al._to_device(torch, dev, a) for a in (rc_tab, pairs, jobs))
+        with d:
+            L, st = d.lib, d.stream
+            d_seq, d_tab, d_pairs, d_jobs = (d.put(a) for a in (clean, rc_tab, pairs, jobs))
             d_scan = torch.empty(4 * R, dtype=torch.int32, device=dev)
             d_flags = torch.empty(flags_bytes, dtype=torch.uint8, device=dev)
             d_out = torch.zeros(8 * J, dtype=torch.int32, device=dev)
             d_runs = torch.zeros(runs_cap, dtype=torch.int32, device=dev)
-            rev_ms = timed(torch, stream, lambda: pkg.engine._check(L.mpc_align_revcomp(
+            rev_ms = tb.timed(d, lambda: d.check(L.mpc_align_revcomp(
                 d_seq.data_ptr(), pk.seq.nbytes, d_tab.data_ptr(), R, st)), args.warmup, args.repeats)
-            scan_ms = timed(torch, stream, lambda: pkg.engine._check(L.mpc_verify_scan(
+            scan_ms = tb.timed(d, lambda: d.check(L.mpc_verify_scan(
                 d_seq.data_ptr(), d_pairs.data_ptr(), 2 * R, d_scan.data_ptr(), st)), args.warmup, args.repeats)
-            trace_ms = timed(torch, stream, lambda: pkg.engine._check(L.mpc_align_trace(
+            trace_ms = tb.timed(d, lambda: d.check(L.mpc_align_trace(
                 d_seq.data_ptr(), pk.seq.nbytes, d_jobs.data_ptr(), J, d_flags.data_ptr(), flags_bytes, d_out.data_ptr(),
                 d_runs.data_ptr(), runs_cap, st)), args.warmup, args.repeats)
-            same = (np.array_equal(d_seq.cpu().numpy(), pk.seq) and
-                    np.array_equal(d_scan.cpu().numpy().reshape(R, 4), host_scan) and
+            same = (np.array_equal(d_seq.cpu().numpy(), host_seq) and np.array_equal(pk.seq, host_seq) and
+                    np.array_equal(d_scan.cpu().numpy().reshape(R, 4), host_scan) and np.array_equal(loop.scan, host_scan) and
+                    np.array_equal(tool_out, host_out) and np.array_equal(tool_runs, host_runs) and
                     np.array_equal(d_out.cpu().numpy().reshape(J, 8), host_out) and
                     np.array_equal(d_runs.cpu().numpy(), host_runs))
             del d_flags
@@ -159,12 +131,8 @@ def main():
                    tool_device_s=round(wall[args.device][0], 3), tool_host_s=round(wall["cpu"][0], 3),
                    tool_device_over_host=round(wall["cpu"][0] / wall[args.device][0], 2),
                    paf_bytes=len(wall["cpu"][1]), gpu=torch.cuda.get_device_name(dev))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+        tb.report(results, rec)
+    tb.write(results, args.out)
 
 
 if __name__ == "__main__":

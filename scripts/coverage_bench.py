@@ -14,18 +14,13 @@ one `rocprofv3 --kernel-trace --stats` run of this script holds K_parse beside
 K_covparse and K_covfinish (the yardstick: both read the same cs bytes).
 Prints one JSON line per config; --out also writes them to a file."""
 import argparse
-import ctypes
-import importlib
-import json
-import os
 import statistics
 import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import _toolbench as tb
 
 # bench.py CONFIGS: (n, reads per sample, profile, seed, plasmids)
 SHAPES = {"c2": (2686, 100_000, "default", 2, 1), "c5": (30_000, 10_000, "default", 5000, 12)}
@@ -43,22 +38,12 @@ def batch(pkg, cfg):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c5"], choices=sorted(SHAPES))
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--pileup-steps", type=int, default=0)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out")
-    args = ap.parse_args()
+    args = tb.parse(ap, repeats=20, warmup=3)
 
-    pkg = importlib.import_module("minion-plasmid-consensus_amd")
-    cov = pkg.coverage
-    L = cov._device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("coverage_bench.py measures on a GPU; none is visible")
+    pkg, d = tb.gpu(args.device)
+    cov, torch, dev = pkg.coverage, d.torch, d.dev
     H = cov.host_lib()
-    dev = torch.device("cuda", args.device)
     results = []
     for cfg in args.configs:
         samples, n = batch(pkg, cfg)
@@ -72,32 +57,20 @@ def main():
         pos_off = (np.arange(S + 1, dtype=np.int64) * (n + 1))
         region = np.tile(np.array([0, n], np.int64), S)
         n_pos = int(pos_off[-1])
-        with torch.cuda.device(dev):
+        with d:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             d_cs, d_off, d_ts, d_rs, d_pos, d_reg = (up(a) for a in (np.concatenate([cs, np.zeros(8, np.uint8)]), cs_off,
                                                                       tstart, rec_sample, pos_off, region))
             d_rows = torch.empty((n_pos, 4), dtype=torch.int32, device=dev)
             d_stats = torch.empty((S, cov.STATS), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev)
 
             def launch():
-                pkg.engine._check(L.mpc_coverage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(),
-                                                     n_rec, d_pos.data_ptr(), d_reg.data_ptr(), S, 0, d_rows.data_ptr(),
-                                                     d_stats.data_ptr(), d_status.data_ptr(),
-                                                     ctypes.c_void_p(stream.cuda_stream)))
+                d.check(d.lib.mpc_coverage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(), n_rec,
+                                               d_pos.data_ptr(), d_reg.data_ptr(), S, 0, d_rows.data_ptr(),
+                                               d_stats.data_ptr(), d_status.data_ptr(), d.stream))
 
-            for _ in range(args.warmup):
-                launch()
-            torch.cuda.synchronize(dev)
-            times = []
-            for _ in range(args.repeats):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                launch()
-                e1.record(stream)
-                e1.synchronize()
-                times.append(e0.elapsed_time(e1) * 1e3)
+            times = [t * 1e3 for t in tb.timed(d, launch, args.warmup, args.repeats)]
             got = (d_rows.cpu().numpy().view(np.uint32), d_stats.cpu().numpy().view(np.uint64), d_status.cpu().numpy())
             if args.pileup_steps:
                 runner = pkg.engine.Runner(samples, device=args.device)
@@ -117,17 +90,13 @@ def main():
                                              and np.array_equal(got[2], status)):
             sys.exit("device and host walks disagree on %s: nothing to report" % cfg)
         med = statistics.median(times)
-        rec = dict(bench="coverage_run", config=cfg, samples=S, records=n_rec, target_len=n, cs_bytes=int(len(cs)),
-                   device_us_min=round(min(times), 1), device_us_median=round(med, 1), device_us_max=round(max(times), 1),
-                   repeats=args.repeats, warmup=args.warmup, cs_gbytes_per_s=round(len(cs) / med / 1e3, 1),
-                   host_threads=args.host_threads, host_ms=round(host_s * 1e3, 1), host_over_device=round(host_s * 1e6 / med, 1),
-                   mean_depth=round(float(stats[0, 7]) / n, 1), gpu=torch.cuda.get_device_name(dev))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+        tb.report(results, dict(
+            bench="coverage_run", config=cfg, samples=S, records=n_rec, target_len=n, cs_bytes=int(len(cs)),
+            device_us_min=round(min(times), 1), device_us_median=round(med, 1), device_us_max=round(max(times), 1),
+            repeats=args.repeats, warmup=args.warmup, cs_gbytes_per_s=round(len(cs) / med / 1e3, 1),
+            host_threads=args.host_threads, host_ms=round(host_s * 1e3, 1), host_over_device=round(host_s * 1e6 / med, 1),
+            mean_depth=round(float(stats[0, 7]) / n, 1), gpu=torch.cuda.get_device_name(dev)))
+    tb.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -16,8 +16,6 @@ Prints one JSON line per set; --out also writes them to a file.  The whole
 tool's wall time (draft.assemble: FASTA, seed, rounds) is reported for the
 device, and for the host path where the sample is at most --host-tool-reads."""
 import argparse
-import importlib
-import json
 import os
 import statistics
 import sys
@@ -26,37 +24,18 @@ import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-
-def event_ms(torch, stream, launch):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    launch()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1)
+import _toolbench as tb
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", nargs="+", default=["2686:500:500", "2686:100000:0"], help="plasmid length:reads in the file:--sample")
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--host-tool-reads", type=int, default=1000, help="largest sample the whole tool is also run on the host for")
-    ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-error", type=float, default=0.3)
-    ap.add_argument("--out")
-    args = ap.parse_args()
+    args = tb.parse(ap, repeats=5, warmup=0)
 
-    pkg = importlib.import_module("minion-plasmid-consensus_amd")
-    al, dr = pkg.align, pkg.draft
-    al.device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("draft_bench.py measures on a GPU; none is visible")
-    dev = torch.device("cuda", args.device)
+    pkg, d = tb.gpu(args.device)
+    al, dr, torch, dev = pkg.align, pkg.draft, d.torch, d.dev
     med = statistics.median
     results = []
     for spec in args.sets:
@@ -74,38 +53,29 @@ def main():
 
             # one round by hand: per launch of the trace, the device vote (timed, repeats into a spare
             # tally) and the host vote of the same tables
-            pk = al.Packed(draft, reads)
-            scan = al.orient_and_scan(pk, args.device, args.host_threads)
-            pl, cuts = al.plan(scan, pk.lens, args.max_error, al.DEFAULT_WORKSPACE)
+            loop = al.Launches(draft, reads, args.device, args.max_error, threads=args.host_threads, keep_device=True)
+            pk, cuts = loop.pk, loop.cuts
             d_tally, d_spare, h_tally = dr.new_tally(n, args.device), dr.new_tally(n, args.device), dr.new_tally(n, "cpu")
-            vote_ms, vote_first_ms, host_vote_s, voted, n_runs, ws = 0.0, 0.0, 0.0, 0, 0, {}
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev)
-                for a, b in zip(cuts[:-1], cuts[1:]):
-                    rd = [r for r in range(a, b) if pl[r, 1]]
-                    jobs = al.jobs_of(pk, pl, rd)
-                    kept = {}
-                    rc, out, runs = al.trace(pk.seq, jobs, args.device, d_seq=pk.d_seq, workspace=ws, device_tensors=kept)
-                    assert rc == 0
+            vote_ms, vote_first_ms, host_vote_s, voted, n_runs = 0.0, 0.0, 0.0, 0, 0
+            with d:
+                for rd, jobs, out, runs, kept in loop:
                     status = []
-                    vote_first_ms += event_ms(torch, stream, lambda: status.append(
-                        dr.vote(d_tally, n, pk.seq, jobs, out, runs, args.device, device_tensors=kept)))
+                    vote_first_ms += tb.timed(d, lambda: status.append(
+                        dr.vote(d_tally, n, pk.seq, jobs, out, runs, args.device, device_tensors=kept)), 0, 1)[0]
                     assert status[0][0] == 0
                     voted += int((status[0][1] == dr.VOTED).sum())
                     n_runs += int(out[:, 6].sum())
-                    vote_ms += med([event_ms(torch, stream, lambda: dr.vote(d_spare, n, pk.seq, jobs, out, runs, args.device,
-                                                                            device_tensors=kept)) for _ in range(args.repeats)])
+                    vote_ms += med(tb.timed(d, lambda: dr.vote(d_spare, n, pk.seq, jobs, out, runs, args.device, device_tensors=kept),
+                                            args.warmup, args.repeats))
                     t0 = time.perf_counter()
                     hrc, hstatus = dr.vote(h_tally, n, pk.seq, jobs, out, runs, "cpu", args.host_threads)
                     host_vote_s += time.perf_counter() - t0
                     assert hrc == 0 and np.array_equal(hstatus, status[0][1])
                 if not np.array_equal(dr.tally_to_host(d_tally), h_tally):
                     sys.exit("device and host tallies differ: nothing to report")
-                call_ms, new = [], None
-                for _ in range(args.repeats + 1):
-                    got = []
-                    call_ms.append(event_ms(torch, stream, lambda: got.append(dr.call(d_tally, draft, args.device, d_draft=pk.d_seq))))
-                    new = got[0]
+                got = []
+                call_ms = tb.timed(d, lambda: got.append(dr.call(d_tally, draft, args.device, d_draft=pk.d_seq)), 1, args.repeats)
+                new = got[0]
                 host_call_s = []
                 for _ in range(3):
                     t0 = time.perf_counter()
@@ -114,7 +84,7 @@ def main():
                 if new != host_new:
                     sys.exit("device and host drafts differ: nothing to report")
             pk.d_seq = None
-            del d_tally, d_spare, ws
+            del d_tally, d_spare, loop
 
             # the whole tool
             wall = {}
@@ -130,17 +100,13 @@ def main():
                    device_vote_ms=round(vote_ms, 3), device_vote_first_ms=round(vote_first_ms, 3),
                    host_threads=args.host_threads, host_vote_ms=round(host_vote_s * 1e3, 3),
                    vote_device_over_host=round(host_vote_s * 1e3 / vote_ms, 2),
-                   device_call_ms=round(med(call_ms[1:]), 3), device_call_ms_min=round(min(call_ms[1:]), 3),
-                   device_call_ms_max=round(max(call_ms[1:]), 3), host_call_ms=round(med(host_call_s) * 1e3, 3),
+                   device_call_ms=round(med(call_ms), 3), device_call_ms_min=round(min(call_ms), 3),
+                   device_call_ms_max=round(max(call_ms), 3), host_call_ms=round(med(host_call_s) * 1e3, 3),
                    new_draft_len=new[1]["length"], tool_device_s=round(wall[args.device][0], 3),
                    tool_host_s=round(wall["cpu"][0], 3) if "cpu" in wall else None,
                    final_draft_len=len(wall[args.device][1]), gpu=torch.cuda.get_device_name(dev))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+        tb.report(results, rec)
+    tb.write(results, args.out)
 
 
 if __name__ == "__main__":

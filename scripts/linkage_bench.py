@@ -15,18 +15,13 @@ One `rocprofv3 --kernel-trace --stats` run of this script gives the per-kernel
 times.  Prints one JSON line per config and site set; --out also writes them
 to a file."""
 import argparse
-import ctypes
-import importlib
-import json
-import os
 import statistics
 import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import _toolbench as tb
 
 # bench.py CONFIGS: (n, reads per sample, profile, seed, plasmids)
 SHAPES = {"c2": (2686, 100_000, "default", 2, 1), "c5": (30_000, 10_000, "default", 5000, 12)}
@@ -41,40 +36,14 @@ def batch(pkg, cfg):
     return samples, n
 
 
-def timed(torch, stream, launch, warmup, repeats):
-    for _ in range(warmup):
-        launch()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        launch()
-        e1.record(stream)
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1) * 1e3)
-    return times
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["c2", "c5"], choices=sorted(SHAPES))
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--host-threads", type=int, default=16)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out")
-    args = ap.parse_args()
+    args = tb.parse(ap, repeats=20, warmup=3)
 
-    pkg = importlib.import_module("minion-plasmid-consensus_amd")
-    cov, lnk = pkg.coverage, pkg.linkage
-    L = lnk._device_lib()
-    cov._device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("linkage_bench.py measures on a GPU; none is visible")
+    pkg, d = tb.gpu(args.device)
+    cov, lnk, torch, dev = pkg.coverage, pkg.linkage, d.torch, d.dev
     H = lnk.host_lib()
-    dev = torch.device("cuda", args.device)
     results = []
     for cfg in args.configs:
         samples, n = batch(pkg, cfg)
@@ -89,22 +58,20 @@ def main():
         region = np.tile(np.array([0, n], np.int64), S)
         regions = [(0, n)] * S
         n_pos = int(pos_off[-1])
-        with torch.cuda.device(dev):
+        with d:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             d_cs, d_off, d_ts, d_rs, d_pos, d_reg = (up(a) for a in (np.concatenate([cs, np.zeros(8, np.uint8)]), cs_off,
                                                                       tstart, rec_sample, pos_off, region))
             d_rows = torch.empty((n_pos, 4), dtype=torch.int32, device=dev)
             d_stats = torch.empty((S, cov.STATS), dtype=torch.int64, device=dev)
             d_status = torch.empty(2, dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            sp = ctypes.c_void_p(stream.cuda_stream)
 
             def cov_launch():
-                pkg.engine._check(L.mpc_coverage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(),
-                                                     n_rec, d_pos.data_ptr(), d_reg.data_ptr(), S, 0, d_rows.data_ptr(),
-                                                     d_stats.data_ptr(), d_status.data_ptr(), sp))
+                d.check(d.lib.mpc_coverage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(), n_rec,
+                                               d_pos.data_ptr(), d_reg.data_ptr(), S, 0, d_rows.data_ptr(),
+                                               d_stats.data_ptr(), d_status.data_ptr(), d.stream))
 
-            cov_times = timed(torch, stream, cov_launch, args.warmup, args.repeats)
+            cov_times = [t * 1e3 for t in tb.timed(d, cov_launch, args.warmup, args.repeats)]
             rows = d_rows.cpu().numpy().view(np.uint32)
             if d_status.cpu().numpy()[0] != 0:
                 sys.exit("coverage_run refuses the %s batch" % cfg)
@@ -118,21 +85,19 @@ def main():
                            coverage_us_min=round(min(cov_times), 1), coverage_us_max=round(max(cov_times), 1))
                 if K == 0:
                     rec["note"] = "no site qualifies: nothing to run"
-                    print(json.dumps(rec), flush=True)
-                    results.append(rec)
+                    tb.report(results, rec)
                     continue
                 d_so, d_sk = up(site_off), up(site_key)
                 d_alleles = torch.empty((n_rec, K), dtype=torch.uint8, device=dev)
                 d_pair = torch.empty((K, K, 8, 8), dtype=torch.int32, device=dev)
-                d_scratch = torch.empty(L.mpc_linkage_scratch_bytes(n_rec, K) // 8, dtype=torch.int64, device=dev)
+                d_scratch = torch.empty(lnk.scratch_bytes(n_rec, K) // 8, dtype=torch.int64, device=dev)
 
                 def launch():
-                    pkg.engine._check(L.mpc_linkage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(), n_rec,
-                                                        d_pos.data_ptr(), S, d_so.data_ptr(), d_sk.data_ptr(), K,
-                                                        d_alleles.data_ptr(), d_pair.data_ptr(), d_scratch.data_ptr(),
-                                                        d_status.data_ptr(), sp))
+                    d.check(d.lib.mpc_linkage_run(d_cs.data_ptr(), d_off.data_ptr(), d_ts.data_ptr(), d_rs.data_ptr(), n_rec,
+                                                  d_pos.data_ptr(), S, d_so.data_ptr(), d_sk.data_ptr(), K, d_alleles.data_ptr(),
+                                                  d_pair.data_ptr(), d_scratch.data_ptr(), d_status.data_ptr(), d.stream))
 
-                times = timed(torch, stream, launch, args.warmup, args.repeats)
+                times = [t * 1e3 for t in tb.timed(d, launch, args.warmup, args.repeats)]
                 got = (d_alleles.cpu().numpy(), d_pair.cpu().numpy().view(np.uint32), d_status.cpu().numpy())
                 alleles = np.zeros((n_rec, K), np.uint8)
                 pair = np.zeros((K, K, 8, 8), np.uint32)
@@ -151,12 +116,8 @@ def main():
                            run_over_coverage_run=round(med / cov_med, 3), host_threads=args.host_threads,
                            host_ms=round(host_s * 1e3, 1), host_over_device=round(host_s * 1e6 / med, 1),
                            gpu=torch.cuda.get_device_name(dev))
-                print(json.dumps(rec), flush=True)
-                results.append(rec)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+                tb.report(results, rec)
+    tb.write(results, args.out)
 
 
 if __name__ == "__main__":

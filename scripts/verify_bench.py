@@ -10,18 +10,13 @@ paths must be equal or nothing is reported.
 
 Prints one JSON line per batch size; --out also writes them to a file."""
 import argparse
-import ctypes
-import importlib
-import json
-import os
 import statistics
 import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import _toolbench as tb
 
 
 def make_pairs(n_pairs, m, seed):
@@ -45,48 +40,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, default=30000)
     ap.add_argument("--pairs", type=int, nargs="+", default=[48, 1])
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--host-threads", type=int, default=16)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out")
-    args = ap.parse_args()
+    args = tb.parse(ap, repeats=7, warmup=2)
 
-    pkg = importlib.import_module("minion-plasmid-consensus_amd")
-    v = pkg.verify
-    L = v.device_lib()
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("verify_bench.py measures on a GPU; none is visible")
+    pkg, d = tb.gpu(args.device)
+    v, torch = pkg.verify, d.torch
     H = v.host_lib()
-    dev = torch.device("cuda", args.device)
     results = []
     for n_pairs in args.pairs:
         pairs = make_pairs(n_pairs, args.m, seed=100 + n_pairs)
         tab, seq = v._pack(pairs)
         cells = int(sum(len(q) * len(t) for q, t in pairs))
-        blob = np.concatenate([tab.reshape(-1).view(np.uint8), seq])
-        d_blob = torch.empty(len(blob), dtype=torch.uint8, device=dev)
-        d_blob.copy_(torch.from_numpy(blob))
-        d_out = torch.empty(2 * n_pairs, dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev)
-
-        def launch():
-            pkg.engine._check(L.mpc_verify_scan(d_blob.data_ptr() + tab.nbytes, d_blob.data_ptr(), n_pairs,
-                                                d_out.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-
-        with torch.cuda.device(dev):
-            for _ in range(args.warmup):
-                launch()
-            torch.cuda.synchronize(dev)
-            times = []
-            for _ in range(args.repeats):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                launch()
-                e1.record(stream)
-                e1.synchronize()
-                times.append(e0.elapsed_time(e1))
+        with d:
+            (at_tab, at_seq), d_blob = d.put_all([tab.reshape(-1), seq])
+            d_out = torch.empty(2 * n_pairs, dtype=torch.int32, device=d.dev)
+            times = tb.timed(d, lambda: d.check(d.lib.mpc_verify_scan(at_seq, at_tab, n_pairs, d_out.data_ptr(), d.stream)),
+                             args.warmup, args.repeats)
             got = d_out.cpu().numpy().reshape(n_pairs, 2)
         host = np.zeros((n_pairs, 2), np.int32)
         t0 = time.perf_counter()
@@ -95,19 +63,15 @@ def main():
         if rc != 0 or not np.array_equal(got, host):
             sys.exit("device and host scans disagree on %d pairs: nothing to report" % n_pairs)
         dev_ms = statistics.median(times)
-        rec = dict(bench="verify_scan", pairs=n_pairs, m=args.m, n=len(pairs[0][1]), dp_cells=cells,
-                   device_ms_median=round(dev_ms, 3), device_ms_min=round(min(times), 3),
-                   device_ms_max=round(max(times), 3), repeats=args.repeats, warmup=args.warmup,
-                   device_cells_per_s=round(cells / (dev_ms * 1e-3), 1),
-                   host_threads=args.host_threads, host_s=round(host_s, 3), host_cells_per_s=round(cells / host_s, 1),
-                   device_over_host=round(host_s / (dev_ms * 1e-3), 2),
-                   gpu=torch.cuda.get_device_name(dev), distances=sorted(set(int(d) for d in got[:, 0])))
-        print(json.dumps(rec), flush=True)
-        results.append(rec)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+        tb.report(results, dict(
+            bench="verify_scan", pairs=n_pairs, m=args.m, n=len(pairs[0][1]), dp_cells=cells,
+            device_ms_median=round(dev_ms, 3), device_ms_min=round(min(times), 3),
+            device_ms_max=round(max(times), 3), repeats=args.repeats, warmup=args.warmup,
+            device_cells_per_s=round(cells / (dev_ms * 1e-3), 1),
+            host_threads=args.host_threads, host_s=round(host_s, 3), host_cells_per_s=round(cells / host_s, 1),
+            device_over_host=round(host_s / (dev_ms * 1e-3), 2),
+            gpu=torch.cuda.get_device_name(d.dev), distances=sorted(set(int(x) for x in got[:, 0]))))
+    tb.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -183,7 +183,7 @@ def run_abi(pkg, packed, pos_off, region, device):
         assert rc == 0, L.mpc_coverage_last_error()
         return tuple(status.tolist()), rows, stats
     import torch
-    L = pkg.coverage._device_lib()
+    L = pkg.engine.lib()
     dev = "cuda:%d" % device
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     d_cs, d_off, d_ts, d_rs, d_pos, d_reg = (up(a) for a in (np.concatenate([cs, np.zeros(8, np.uint8)]), off, ts, rs,

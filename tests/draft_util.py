@@ -148,18 +148,9 @@ def traced(pkg, target, reads, device, workspace_bytes=None, threads=2):
     """The reads aligned to the target as a round does it: [(pk, jobs, out,
     runs, kept, read indices)] per launch, and the plan."""
     al = pkg.align
-    pk = al.Packed(target, reads)
-    scan = al.orient_and_scan(pk, device, threads)
-    pl, cuts = al.plan(scan, pk.lens, MAX_ERROR, workspace_bytes if workspace_bytes is not None else al.DEFAULT_WORKSPACE)
-    launches = []
-    for a, b in zip(cuts[:-1], cuts[1:]):
-        rd = [r for r in range(a, b) if pl[r, 1]]
-        jobs = al.jobs_of(pk, pl, rd)
-        kept = {}
-        rc, out, runs = al.trace(pk.seq, jobs, device, threads, d_seq=pk.d_seq, device_tensors=kept)
-        assert rc == 0
-        launches.append((pk, jobs, out, runs, kept, rd))
-    return launches, pl
+    loop = al.Launches(target, reads, device, MAX_ERROR, workspace_bytes if workspace_bytes is not None else al.DEFAULT_WORKSPACE,
+                       threads, keep_device=True)
+    return [(loop.pk, jobs, out, runs, kept or {}, rd) for rd, jobs, out, runs, kept in loop], loop.plan
 
 
 def checker_reads(launch, skip=()):

@@ -459,7 +459,7 @@ def run_abi(pkg, packed, pos_off, site_off, site_key, device):
         assert rc == 0, L.mpc_linkage_last_error()
         return tuple(status.tolist()), alleles, pair
     import torch
-    L = pkg.linkage._device_lib()
+    L = pkg.engine.lib()
     dev = "cuda:%d" % device
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     d_cs, d_off, d_ts, d_rs, d_pos, d_so, d_sk = (up(a) for a in (cs, off, ts, rs, pos_off, site_off, site_key))
@@ -559,23 +559,15 @@ def case_planted_cli(pkg, device, tmp_path, cli):
     return outs
 
 
-def case_sanitized_driver(pkg, tmp_path, repo):
+def case_sanitized_driver(pkg, tmp_path):
     """ASan + UBSan on the host code, as a stand-alone program; no recovery: any report, a leak included, fails the run."""
-    import os
-    import subprocess
-    csrc = os.path.join(repo, "minion-plasmid-consensus_amd", "csrc")
-    drv, exe, data = tmp_path / "lnk_driver.cpp", tmp_path / "lnk_asan", tmp_path / "planted.txt"
+    import native_util as nu
+    drv, data = tmp_path / "lnk_driver.cpp", tmp_path / "planted.txt"
     drv.write_text(DRIVER)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-pthread", "-I", os.path.join(repo, "include"), "-I", csrc, "-o", str(exe),
-                    os.path.join(csrc, "linkage.cpp"), str(drv)], check=True)
+    exe = nu.build("lnk_asan", ["linkage.cpp", drv], ["-pthread"])
     records, carrier, sub80, sub160 = planted()
     data.write_bytes(b"".join(b"%d\t%s\n" % (ts, cs) for _, ts, cs in records))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
-    p = subprocess.run([str(exe), str(data)], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, (p.returncode, p.stdout[-500:], p.stderr[-3000:])
-    out = p.stdout.splitlines()
+    out = nu.run(exe, [data]).splitlines()
     diag = [2000 - int(v.sum()) for v in (carrier, sub80, carrier, sub160, carrier)]
     want = "records 2000 status 0 0 joint 200 200 200 diag " + " ".join(map(str, diag))
     assert out[:2] == ["threads 1 " + want, "threads 4 " + want]

@@ -7,38 +7,20 @@ launches.  Any sanitizer report, a leak included, fails the run (non-zero
 exit); what it prints must equal what the checker of tests/align_util.py says
 (CPU only, no HIP; nothing is loaded into Python under a sanitizer)."""
 import os
-import subprocess
 
 import pytest
 
 import align_util as au
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "build", "align_asan")
+import native_util as nu
 
 
 @pytest.fixture(scope="module")
 def asan_bin():
-    os.makedirs(os.path.dirname(BIN), exist_ok=True)
-    csrc = os.path.join(REPO, "minion-plasmid-consensus_amd", "csrc")
-    src = [os.path.join(csrc, "align.cpp"), os.path.join(csrc, "verify.cpp"),
-           os.path.join(REPO, "tests", "native", "align_driver.cpp")]
-    # build under a per-process name, then rename: pytest-xdist workers each
-    # build it, and one must never exec a file another is still writing
-    tmp = "%s.%d" % (BIN, os.getpid())
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-pthread", "-I", os.path.join(REPO, "include"), "-I", csrc, "-o", tmp] + src,
-                   check=True)
-    os.replace(tmp, BIN)
-    return BIN
+    return nu.build("align_asan", ["align.cpp", "verify.cpp", os.path.join(nu.NATIVE, "align_driver.cpp")], ["-pthread"])
 
 
 def _run(asan_bin, path):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
-    p = subprocess.run([asan_bin, path], capture_output=True, env=env, timeout=300)
-    assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
-    return p.stdout
+    return nu.run(asan_bin, [path], text=False)
 
 
 def _case_file(path, batches, budget):

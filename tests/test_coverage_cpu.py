@@ -12,6 +12,7 @@ import pytest
 
 import cov_util as cu
 import glue_cases as gc
+import native_util as nu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(REPO, "minion-plasmid-consensus_amd", "coverage_qc.py")
@@ -364,22 +365,15 @@ int main(int argc, char** argv) {
 
 def test_host_code_sanitized(pkg, paf_files, tmp_path):
     """ASan + UBSan, no recovery: any report, a leak included, fails the run."""
-    csrc = os.path.join(REPO, "minion-plasmid-consensus_amd", "csrc")
-    drv, exe = tmp_path / "cov_driver.cpp", tmp_path / "cov_asan"
+    drv = tmp_path / "cov_driver.cpp"
     drv.write_text(DRIVER)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-pthread", "-I", os.path.join(REPO, "include"), "-I", csrc, "-o", str(exe),
-                    os.path.join(csrc, "coverage.cpp"), str(drv)], check=True)
+    exe = nu.build("cov_asan", ["coverage.cpp", drv], ["-pthread"])
     lines = _lines(paf_files[0][0])
     dup = tmp_path / "dup.paf"
     dup.write_bytes(b"\n".join(lines + [lines[5]]) + b"\n")
     bad = tmp_path / "bad.paf"
     bad.write_bytes(lines[0] + b"\n" + b"\t".join(lines[1].split(b"\t")[:9]))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
-    p = subprocess.run([str(exe), str(dup), str(bad)], capture_output=True, text=True, env=env, timeout=300)
-    assert p.returncode == 0, (p.returncode, p.stdout[-500:], p.stderr[-3000:])
-    out = p.stdout.splitlines()
+    out = nu.run(exe, [dup, bad]).splitlines()
     smp = paf_files[1][0]
     records = [(0, int(smp["tstart"][r]), smp["cs"].tobytes()[smp["cs_off"][r]:smp["cs_off"][r + 1]]) for r in range(300)]
     for mode, recs in ((0, records), (1, records + [records[5]])):

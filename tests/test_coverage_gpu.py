@@ -178,7 +178,7 @@ def test_sample_index_outside_the_targets(pkg):
 
 def test_run_refuses_bad_tables_before_launch(pkg):
     import torch
-    L = pkg.coverage._device_lib()
+    L = pkg.engine.lib()
     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device="cuda:0")
     cs = torch.zeros(16, dtype=torch.uint8, device="cuda:0")
     rows = torch.full((11 * 4,), -5, dtype=torch.int32, device="cuda:0")

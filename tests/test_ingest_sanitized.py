@@ -7,17 +7,13 @@ with 1 and 8 threads.  Any sanitizer report fails the run (non-zero exit); the
 digests of its outputs must equal those of the production library (CPU only)."""
 import importlib
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import golden_util as gu
+import native_util as nu
 import test_ingest_native as tin
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "build", "ingest_asan")
 
 
 def _fnv(a):
@@ -32,19 +28,8 @@ def _fnv(a):
 
 @pytest.fixture(scope="module")
 def asan_bin():
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    os.makedirs(os.path.dirname(BIN), exist_ok=True)
-    src = [os.path.join(REPO, "minion-plasmid-consensus_amd", "csrc", f) for f in
-           ("ingest.cpp", "writers.cpp", "pseudopair.cpp")] + [os.path.join(REPO, "tests", "native", "ingest_driver.cpp")]
-    # build under a per-process name, then rename: pytest-xdist workers each
-    # build it, and one must never exec a file another is still writing
-    tmp = "%s.%d" % (BIN, os.getpid())
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-pthread", "-I", os.path.join(REPO, "include"), "-o", tmp] + src,
-                   check=True)
-    os.replace(tmp, BIN)
-    return BIN
+    return nu.build("ingest_asan", ["ingest.cpp", "writers.cpp", "pseudopair.cpp", os.path.join(nu.NATIVE, "ingest_driver.cpp")],
+                    ["-pthread"])
 
 
 def _expect(ing, ref, paf, reads):
@@ -63,12 +48,8 @@ def _expect(ing, ref, paf, reads):
 
 def _run(asan_bin, ing, ref, paf, reads, threads=(1, 8)):
     exp = _expect(ing, ref, paf, reads)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
     for t in threads:
-        p = subprocess.run([asan_bin, ref, paf, reads, str(t)], capture_output=True, text=True, env=env, timeout=120)
-        assert p.returncode == 0, (ref, t, p.returncode, p.stderr[-2000:])
-        got = p.stdout.strip()
+        got = nu.run(asan_bin, [ref, paf, reads, t], timeout=120).strip()
         if exp in ("1", "2"):
             assert got.split()[0] == exp, (ref, got)
         else:
@@ -105,18 +86,11 @@ def test_synthetic_sanitized(asan_bin, ing, tmp_path):
     _run(asan_bin, ing, p["ras.fa"], p["as.paf"], p["reads.fa"])
 
 
-def _san_env():
-    return dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
-
-
 def test_writers_sanitized(asan_bin, tmp_path):
     w = importlib.import_module("minion-plasmid-consensus_amd.writers")
     for n in (0, 1, 5000, 40000):
         outs = [str(tmp_path / ("%s%d" % (x, n))) for x in ("c", "ch", "acc")]
-        p = subprocess.run([asan_bin, "writecalls", str(n), "7", *outs], capture_output=True, text=True,
-                           env=_san_env(), timeout=120)
-        assert p.returncode == 0 and p.stdout.strip() == "0", (n, p.stderr[-2000:])
+        assert nu.run(asan_bin, ["writecalls", n, 7, *outs], timeout=120).strip() == "0", n
         assert open(outs[0]).read().startswith(">consensus\n")
         assert open(outs[1]).read().count("\n") == 1 + 2 * n
     assert w is not None
@@ -129,10 +103,7 @@ def test_pseudopair_sanitized(asan_bin, tmp_path):
         paf = tmp_path / (case + ".paf")
         paf.write_bytes(tp.read(case, "in.paf"))
         out = tmp_path / (case + ".out")
-        p = subprocess.run([asan_bin, "pseudopair", str(paf), "0", str(out)], capture_output=True, text=True,
-                           env=_san_env(), timeout=120)
-        assert p.returncode == 0, (case, p.stderr[-2000:])
-        status = int(p.stdout.split()[0])
+        status = int(nu.run(asan_bin, ["pseudopair", paf, 0, out], timeout=120).split()[0])
         try:
             st = pp.pseudopair_native(str(paf), 0, str(tmp_path / "ref.out"))
             exp = 2 if st is None else 0

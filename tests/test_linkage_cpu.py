@@ -169,4 +169,4 @@ def test_synth_batch_site_count(pkg):
 
 
 def test_host_code_sanitized(pkg, tmp_path):
-    lu.case_sanitized_driver(pkg, tmp_path, REPO)
+    lu.case_sanitized_driver(pkg, tmp_path)

@@ -45,7 +45,7 @@ def test_pairs_limits(pkg):
 
 def test_pairs_refuses_129_sites_untouched(pkg):
     import torch
-    L = pkg.linkage._device_lib()
+    L = pkg.engine.lib()
     alleles = torch.ones((4, 129), dtype=torch.uint8, device="cuda:0")
     pair = torch.full((64,), -5, dtype=torch.int32, device="cuda:0")
     scratch = torch.full((64,), -5, dtype=torch.int64, device="cuda:0")
@@ -79,7 +79,7 @@ def test_sample_index_outside_the_targets(pkg):
 
 def test_run_refuses_bad_tables_before_launch(pkg):
     import torch
-    L = pkg.linkage._device_lib()
+    L = pkg.engine.lib()
     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device="cuda:0")
     cs = torch.zeros(16, dtype=torch.uint8, device="cuda:0")
     cs[:2] = torch.tensor(list(b":3"), dtype=torch.uint8)

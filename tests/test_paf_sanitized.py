@@ -10,30 +10,16 @@ the files' own text say (CPU only, no HIP; nothing is loaded into Python under
 a sanitizer)."""
 import importlib
 import os
-import subprocess
 
 import pytest
 
 import glue_cases as gc
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "build", "paf_asan")
+import native_util as nu
 
 
 @pytest.fixture(scope="module")
 def asan_bin():
-    os.makedirs(os.path.dirname(BIN), exist_ok=True)
-    csrc = os.path.join(REPO, "minion-plasmid-consensus_amd", "csrc")
-    src = [os.path.join(csrc, "coverage.cpp"), os.path.join(csrc, "pseudopair.cpp"),
-           os.path.join(REPO, "tests", "native", "paf_driver.cpp")]
-    # build under a per-process name, then rename: pytest-xdist workers each
-    # build it, and one must never exec a file another is still writing
-    tmp = "%s.%d" % (BIN, os.getpid())
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-pthread", "-I", os.path.join(REPO, "include"), "-I", csrc, "-o", tmp] + src,
-                   check=True)
-    os.replace(tmp, BIN)
-    return BIN
+    return nu.build("paf_asan", ["coverage.cpp", "pseudopair.cpp", os.path.join(nu.NATIVE, "paf_driver.cpp")], ["-pthread"])
 
 
 def test_paf_readers_sanitized(asan_bin, tmp_path):
@@ -41,11 +27,7 @@ def test_paf_readers_sanitized(asan_bin, tmp_path):
     paths = gc.write_paf_files(tmp_path)
     names = sorted(paths)
     missing = str(tmp_path / "missing.paf")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
-    p = subprocess.run([asan_bin, str(tmp_path / "pairs.txt")] + [paths[n] for n in names] + [missing], capture_output=True,
-                       text=True, env=env, timeout=300)
-    assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
+    got = nu.run(asan_bin, [tmp_path / "pairs.txt"] + [paths[n] for n in names] + [missing])
     want = []
     for i, name in enumerate(names):
         lines = [ln.split("\t") for ln in gc.PAF_FILES[name].split("\n") if ln]
@@ -59,4 +41,4 @@ def test_paf_readers_sanitized(asan_bin, tmp_path):
         want.append("cov %d threads %d rc 1 records 0 lines 0 targets 0 cs_sum 0 message %s: cannot be read" % (
             len(names), threads, missing))
         want.append("pp %d threads %d rc 1 fwd 0 rev 0 kept 0 0 pairs 0 message cannot open %s" % (len(names), threads, missing))
-    assert p.stdout.splitlines() == want
+    assert got.splitlines() == want

@@ -6,7 +6,6 @@ csrc/verify.cpp through a stand-alone driver."""
 import ctypes
 import os
 import re
-import shutil
 import statistics
 import subprocess
 import sys
@@ -14,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import native_util as nu
 import verify_util as vu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -299,8 +299,6 @@ def test_verify_header_exports(pkg):
 # ---- sanitizers (host code, stand-alone program) ------------------------------
 
 def test_verify_host_code_sanitized(grid, tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
     pairs, ref = grid
     picked = [k for k in range(len(pairs)) if k % 4 == 0 and b"\t" not in pairs[k][0] + pairs[k][1]]
     rng = np.random.default_rng(31)
@@ -310,21 +308,9 @@ def test_verify_host_code_sanitized(grid, tmp_path):
     want = [vu.traceback(q, t) for q, t in use[:-1]]
     inp = tmp_path / "pairs.txt"
     inp.write_bytes(b"".join(q + b"\t" + t + b"\n" for q, t in use))
-    out = os.path.join(REPO, "build")
-    os.makedirs(out, exist_ok=True)
-    binary = os.path.join(out, "verify_asan")
-    tmp = "%s.%d" % (binary, os.getpid())
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-pthread", "-I", os.path.join(REPO, "include"), "-o", tmp,
-                    os.path.join(REPO, "minion-plasmid-consensus_amd", "csrc", "verify.cpp"),
-                    os.path.join(REPO, "tests", "native", "verify_driver.cpp")], check=True)
-    os.replace(tmp, binary)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
+    binary = nu.build("verify_asan", ["verify.cpp", os.path.join(nu.NATIVE, "verify_driver.cpp")], ["-pthread"])
     for threads in (1, 4):
-        p = subprocess.run([binary, str(inp), str(threads)], capture_output=True, text=True, env=env, timeout=120)
-        assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
-        got = p.stdout.splitlines()
+        got = nu.run(binary, [inp, threads], timeout=120).splitlines()
         assert len(got) == len(use)
         for line, r in zip(got, want):
             assert line == "%d %d %d %d %d %d %d %s" % ((r["distance"], r["end"], r["start"]) + tuple(vu.op_counts(r["ops"])) + (vu.cigar(r["ops"]),))
