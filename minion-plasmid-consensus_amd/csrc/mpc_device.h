@@ -87,6 +87,42 @@ __device__ __forceinline__ int wave_scan_max_i32(int x) {
   x = max(x, dpp_i32<0x143, 0xc>(x));
   return x;
 }
+// The workgroup prefix sum, stated once: inclusive prefix sums (32-bit, wrapping)
+// of NV ints per thread over the NW waves of the block; total[k] = the block's
+// sum, in every thread.  Each wave scans, lane 63 leaves the wave's totals in
+// s_w (NV x NW ints of LDS), and after ONE barrier every thread adds the totals
+// of the waves before its own.  Every thread of the block calls it (NW =
+// blockDim.x / 64).  The CALLER places a barrier between a call and the next
+// write of the same s_w (the next call): the call leaves reading s_w.
+template <int NW, int NV>
+__device__ __forceinline__ void block_scan(const int (&v)[NV], int (&incl)[NV], int (&total)[NV], int32_t (*s_w)[NW]) {
+  const int w = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int k = 0; k < NV; ++k) incl[k] = wave_scan_i32(v[k]);
+  if (lane() == 63)
+    for (int k = 0; k < NV; ++k) s_w[k][w] = incl[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    int all = 0;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+      const int x = s_w[k][j];
+      if (j < w) incl[k] += x;
+      all += x;
+    }
+    total[k] = all;
+  }
+}
+// (one value: the same code)
+template <int NW>
+__device__ __forceinline__ int block_scan(int v, int& total, int32_t (&s_w)[NW]) {
+  const int vv[1] = {v};
+  int incl[1], tot[1];
+  block_scan<NW, 1>(vv, incl, tot, &s_w);
+  total = tot[0];
+  return incl[0];
+}
 __device__ __forceinline__ int wave_last_i32(int x) { return __builtin_amdgcn_readlane(x, 63); }
 __device__ __forceinline__ int uniform_i32(int x) { return __builtin_amdgcn_readfirstlane(x); }
 

@@ -136,31 +136,12 @@ __global__ __launch_bounds__(64) void K_dvote(const uint8_t* __restrict__ seq, c
   }
 }
 
-// Inclusive prefix sum of v over the workgroup's 1024 threads (16 waves); *total = the sum.
-// wsum: 16 ints of LDS.  Every thread calls it.
-__device__ __forceinline__ int block_scan(int v, int* wsum, int* total) {
-  const int w = (int)(threadIdx.x >> 6);
-  const int s = wave_scan_i32(v);
-  __syncthreads();  // the previous call's wsum is no longer read
-  if (lane() == 63) wsum[w] = s;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kCallThreads / 64; ++k) {
-    const int x = wsum[k];
-    before += k < w ? x : 0;
-    all += x;
-  }
-  *total = all;
-  return s + before;
-}
-
 // grid: ONE 1024-thread workgroup
 __global__ __launch_bounds__(kCallThreads) void K_dcall(const uint32_t* __restrict__ tally, const uint8_t* __restrict__ draft,
                                                         const int n, uint8_t* __restrict__ fresh, const int64_t fresh_cap,
                                                         int32_t* __restrict__ work, int32_t* __restrict__ info) {
-  __shared__ int wsum[kCallThreads / 64];
-  __shared__ int red[3][kCallThreads / 64];
+  constexpr int NW = kCallThreads / 64;
+  __shared__ int32_t s_w[3][NW];  // block_scan's wave totals, then the reductions' (a barrier between any two uses)
   const int tid = (int)threadIdx.x;
   int32_t* cov = work;
   int32_t* eq = work + (n + 1);
@@ -170,28 +151,26 @@ __global__ __launch_bounds__(kCallThreads) void K_dcall(const uint32_t* __restri
   int c_cov = 0, c_eq = 0, c_del = 0, mx = 0;
   for (int j0 = 0; j0 < n; j0 += kCallThreads) {
     const int j = j0 + tid;
-    int a = 0, b = 0, c = 0;
+    int v[3] = {0, 0, 0}, inc[3], tot[3];
     if (j < n) {
       const uint32_t* row = tally + (int64_t)j * MPC_DRAFT_ROW;
-      a = (int)(row[kStarts] - row[kEnds]);
-      b = (int)(row[kEqOn] - row[kEqOff]);
-      c = (int)(row[kDelOn] - row[kDelOff]);
+      v[0] = (int)(row[kStarts] - row[kEnds]);
+      v[1] = (int)(row[kEqOn] - row[kEqOff]);
+      v[2] = (int)(row[kDelOn] - row[kDelOff]);
     }
-    int ta, tb, tc;
-    a = c_cov + block_scan(a, wsum, &ta);
-    b = c_eq + block_scan(b, wsum, &tb);
-    c = c_del + block_scan(c, wsum, &tc);
-    c_cov += ta; c_eq += tb; c_del += tc;
+    block_scan<NW, 3>(v, inc, tot, s_w);
     if (j < n) {
-      cov[j] = a; eq[j] = b; del[j] = c;
-      mx = max(mx, a);
+      cov[j] = c_cov + inc[0]; eq[j] = c_eq + inc[1]; del[j] = c_del + inc[2];
+      mx = max(mx, c_cov + inc[0]);
     }
+    c_cov += tot[0]; c_eq += tot[1]; c_del += tot[2];
+    __syncthreads();  // s_w: the next pass, the maximum below
   }
   mx = wave_max(mx);
-  if (lane() == 0) red[0][tid >> 6] = mx;
+  if (lane() == 0) s_w[0][tid >> 6] = mx;
   __syncthreads();
   int maxcov = 0;
-  for (int k = 0; k < kCallThreads / 64; ++k) maxcov = max(maxcov, red[0][k]);
+  for (int k = 0; k < NW; ++k) maxcov = max(maxcov, s_w[0][k]);
   if (maxcov == 0) {
     if (tid < 8) info[tid] = tid == 0 ? MPC_DRAFT_EMPTY : 0;
     return;
@@ -207,9 +186,9 @@ __global__ __launch_bounds__(kCallThreads) void K_dcall(const uint32_t* __restri
   lo = -wave_max(-lo);
   hi = wave_max(hi);
   __syncthreads();
-  if (lane() == 0) { red[1][tid >> 6] = lo; red[2][tid >> 6] = hi; }
+  if (lane() == 0) { s_w[1][tid >> 6] = lo; s_w[2][tid >> 6] = hi; }
   __syncthreads();
-  for (int k = 0; k < kCallThreads / 64; ++k) { lo = min(lo, red[1][k]); hi = max(hi, red[2][k]); }
+  for (int k = 0; k < NW; ++k) { lo = min(lo, s_w[1][k]); hi = max(hi, s_w[2][k]); }
 
   // the columns, a tile of 1024 at a time: emitted length, exclusive scan, write
   int at = 0, changed = 0, dropped = 0, inserted = 0;
@@ -219,20 +198,21 @@ __global__ __launch_bounds__(kCallThreads) void K_dcall(const uint32_t* __restri
     if (j < hi) em = call_column(tally + (int64_t)j * MPC_DRAFT_ROW, draft[j], cov[j], eq[j], del[j], j > lo);
     const int cnt = em.n_ins + (em.col >= 0 ? 1 : 0);
     int total;
-    int64_t p = (int64_t)at + block_scan(cnt, wsum, &total) - cnt;
+    __syncthreads();  // s_w: the pass before (the first: lo / hi above share its rows 1, 2 only)
+    int64_t p = (int64_t)at + block_scan(cnt, total, s_w[0]) - cnt;
     at += total;
     for (int s = 0; s < em.n_ins; ++s, ++p)
       if (p < fresh_cap) fresh[p] = (uint8_t)(em.ins >> (8 * s));
     if (em.col >= 0 && p < fresh_cap) fresh[p] = (uint8_t)em.col;
     changed += em.changed; dropped += em.dropped; inserted += em.n_ins;
   }
-  int t_changed, t_dropped, t_inserted;
-  block_scan(changed, wsum, &t_changed);
-  block_scan(dropped, wsum, &t_dropped);
-  block_scan(inserted, wsum, &t_inserted);
+  const int v[3] = {changed, dropped, inserted};
+  int inc[3], tot[3];
+  __syncthreads();  // s_w: the last pass, lo / hi
+  block_scan<NW, 3>(v, inc, tot, s_w);
   if (tid == 0) {
     info[0] = at > MPC_DRAFT_MAX_LEN ? MPC_DRAFT_LONG : MPC_DRAFT_CALLED;
-    info[1] = at; info[2] = lo; info[3] = hi; info[4] = maxcov; info[5] = t_changed; info[6] = t_dropped; info[7] = t_inserted;
+    info[1] = at; info[2] = lo; info[3] = hi; info[4] = maxcov; info[5] = tot[0]; info[6] = tot[1]; info[7] = tot[2];
   }
 }
 

@@ -144,8 +144,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kCR > 1 ? 4
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void K_select(Dev d, int64_t R, uint32_t epoch) {
   __shared__ int32_t srow[kSmpLds];
   __shared__ uint32_t smd[kSmpLds];
-  __shared__ int32_t s_w[4];
-  __shared__ int64_t s_pre;
+  __shared__ int32_t s_w[1][4];
+  __shared__ int64_t s_pre[1];
   load_sample_rows(d, srow);
   for (int s = threadIdx.x; s < d.S && s < kSmpLds; s += blockDim.x) smd[s] = d.maxdepth[s];
   const int64_t b = blockIdx.x;
@@ -165,21 +165,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void K
       if ((double)v[k].y > thr) { ++c; bits |= 1u << k; }  // :428
     }
   }
-  const int w = threadIdx.x >> 6, l = lane();
-  const int inc = wave_scan_i32(c);
-  if (l == 63) s_w[w] = inc;
-  __syncthreads();
-  int32_t wpre = 0, bt = 0;
-  for (int k = 0; k < 4; ++k) { wpre += k < w ? s_w[k] : 0; bt += s_w[k]; }
-  const uint64_t tag = (uint64_t)(epoch & 0x3fffffffu) << 32;
-  if (w == 0) {
-    int64_t pr;
-    lookback<1>(reinterpret_cast<uint64_t*>(d.ksum), b, tag, &bt, &pr, &d.status[MPC_ST_FLAGS]);
-    if (l == 0) s_pre = pr;
-  }
-  __syncthreads();
-  const int64_t pre = s_pre;
-  int64_t pos = pre + wpre + inc - c;
+  const int cv[1] = {c};
+  int inc[1], bt[1];
+  int64_t pre[1];
+  chain_scan<4, 1>(reinterpret_cast<uint64_t*>(d.ksum), b, epoch, cv, inc, bt, pre, s_w, s_pre, &d.status[MPC_ST_FLAGS]);
+  int64_t pos = pre[0] + inc[0] - c;
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (bits & (1u << k)) {
@@ -187,11 +177,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void K
       reinterpret_cast<uint4*>(d.calls)[pos++] = make_uint4(x.x & 0xffffffu, x.y, x.z, x.w);
     }
   // ncalls[s] = calls before the first row of sample s; ncalls[S] = all
-  const int64_t b0 = b * kKB, all = pre + bt;
+  const int64_t b0 = b * kKB, all = pre[0] + bt[0];
   for (int s = 0; s < d.S; ++s) {
     const int64_t rb = s < kSmpLds ? srow[s] : d.srow[s];
     if (rb >= b0 && rb < b0 + kKB && (rb - b0) / 4 == threadIdx.x) {
-      int64_t q = pre + wpre + inc - c;
+      int64_t q = pre[0] + inc[0] - c;
       for (int k = 0; k < (int)((rb - b0) & 3); ++k) q += (bits >> k) & 1u;
       d.ncalls[s] = (int32_t)q;
     }

@@ -1,6 +1,7 @@
 // What every stage of the pileup path (mpc_k_*.h, one translation unit:
 // mpc_kernels.hip) shares: the error flags, the 32-bit coordinate caps, the
-// decoupled look-back of K_layout / K_select, the insertion event word, Dev
+// decoupled look-back and the chained scan of K_runs / K_layout / K_select, the
+// insertion event word, Dev
 // (the device-side views of a plan) with its host filler plan_dev, the codes of
 // a written cs byte, wave idioms and the stamp macros of the diagnostic builds.
 #pragma once
@@ -97,6 +98,27 @@ __device__ void lookback(uint64_t* st, int64_t b, uint64_t tag, const int32_t* o
       __hip_atomic_store(st + NV * b + k, kSelPre | tag | (uint32_t)(int32_t)(acc[k] + own[k]), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
   for (int k = 0; k < NV; ++k) pre[k] = acc[k];
+}
+
+// The chained scan of K_runs, K_layout and K_select, called by every thread of
+// block b: block_scan, then wave 0 chains the block's totals (lookback, tagged
+// with the launch epoch) and broadcasts the exclusive prefixes through s_pre
+// (NV words of LDS).  Per value: incl = the thread's inclusive prefix within the
+// block, total = the block's sum, pre = the sum of the blocks before.  Two
+// barriers; s_w and s_pre as block_scan's s_w (one call per launch today).
+template <int NW, int NV>
+__device__ __forceinline__ void chain_scan(uint64_t* st, int64_t b, uint32_t epoch, const int (&v)[NV], int (&incl)[NV],
+                                           int (&total)[NV], int64_t (&pre)[NV], int32_t (*s_w)[NW], int64_t* s_pre,
+                                           uint32_t* flags) {
+  block_scan<NW, NV>(v, incl, total, s_w);
+  if (threadIdx.x < 64) {
+    int64_t p[NV];
+    lookback<NV>(st, b, (uint64_t)(epoch & 0x3fffffffu) << 32, total, p, flags);
+    if (lane() == 0)
+      for (int k = 0; k < NV; ++k) s_pre[k] = p[k];
+  }
+  __syncthreads();
+  for (int k = 0; k < NV; ++k) pre[k] = s_pre[k];
 }
 
 // WoEv.type of a string in a wrapped odd position (the records: mpc_geometry.h)

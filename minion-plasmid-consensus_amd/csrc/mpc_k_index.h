@@ -21,7 +21,7 @@ __device__ __forceinline__ bool l_is(int j) { return lane() == j; }
 __device__ __forceinline__ void rsplit_block(const Dev& d, int64_t b) {
   __shared__ int64_t s_key;
   __shared__ int32_t s_val;
-  __shared__ int32_t s_w[16];
+  __shared__ int32_t s_w[kRS / 64];
   const int64_t r = b * blockDim.x + threadIdx.x;
   const bool in = r < d.N;
   int64_t g = -1;
@@ -41,15 +41,10 @@ __device__ __forceinline__ void rsplit_block(const Dev& d, int64_t b) {
     d.rlen[rg] = len;
   }
   // block-local stable compaction of the mixed events (read order), for K_rsort
-  const int f = mixed ? 1 : 0;
-  const int inc = wave_scan_i32(f);
-  const int w = threadIdx.x >> 6;
-  if (lane() == 63) s_w[w] = inc;
-  __syncthreads();
-  int wpre = 0;
-  for (int k = 0; k < w; ++k) wpre += s_w[k];
+  int bt;
+  const int inc = block_scan(mixed ? 1 : 0, bt, s_w);
   if (mixed) {
-    const int64_t o = b * blockDim.x + wpre + inc - 1;
+    const int64_t o = b * blockDim.x + inc - 1;
     d.keys_in[o] = (uint32_t)g;
     d.vals_in[o] = (int32_t)rg;
   }
@@ -61,11 +56,11 @@ __device__ __forceinline__ void rsplit_block(const Dev& d, int64_t b) {
       int32_t base = 0;
       if (l_is(lead)) base = atomicAdd(d.gcnt + gl, __popcll(same));
       base = __builtin_amdgcn_readlane(base, lead);
-      if (mixed && (int32_t)g == gl) d.kslot[b * blockDim.x + wpre + inc - 1] = base + lanes_below(same);
+      if (mixed && (int32_t)g == gl) d.kslot[b * blockDim.x + inc - 1] = base + lanes_below(same);
       act &= ~same;
     }
   }
-  if (threadIdx.x == blockDim.x - 1) d.bcnt[b] = wpre + inc;
+  if (threadIdx.x == 0) d.bcnt[b] = bt;
   block_atomic_max(d.maxR, g < 0 ? 0 : g, len, in && g >= 0 && !mixed, &s_key, &s_val);
 }
 
@@ -220,30 +215,24 @@ __global__ __launch_bounds__(kRS) void K_rsort(Dev d, int32_t nblocks, int32_t e
   __shared__ int32_t wc[kRS / 64][256];
   __shared__ int32_t hb[256];
   __shared__ int32_t s_w[kRS / 64];
-  __shared__ int32_t s_carry;
   __shared__ int32_t s_bpre[kGatherLds + 1];
   const int tid = threadIdx.x, l = lane(), w = tid >> 6;
   const bool pre_lds = nblocks <= kGatherLds;
   // exclusive prefix of the per-block counts -> bpre[0..nblocks]
-  if (tid == 0) s_carry = 0;
-  __syncthreads();
+  int carry = 0;
   for (int c0 = 0; c0 < nblocks; c0 += kRS) {
     const int b = c0 + tid;
     const int v = b < nblocks ? d.bcnt[b] : 0;
-    const int inc = wave_scan_i32(v);
-    if (l == 63) s_w[w] = inc;
-    __syncthreads();
-    int pre = s_carry;
-    for (int k = 0; k < w; ++k) pre += s_w[k];
+    int tot;
+    const int pre = carry + block_scan(v, tot, s_w) - v;
+    carry += tot;
     if (b < nblocks) {
-      d.bpre[b] = pre + inc - v;
-      if (pre_lds) s_bpre[b] = pre + inc - v;
+      d.bpre[b] = pre;
+      if (pre_lds) s_bpre[b] = pre;
     }
-    __syncthreads();
-    if (tid == kRS - 1) s_carry = pre + inc;
-    __syncthreads();
+    __syncthreads();  // s_w: the next pass
   }
-  const int64_t M = s_carry;
+  const int64_t M = carry;
   if (tid == 0) { d.bpre[nblocks] = (int32_t)M; d.status[MPC_ST_MIXED] = (uint32_t)M; }
   if (M == 0) return;
   const int passes = (end_bit + 7) / 8;
@@ -392,7 +381,7 @@ __global__ __launch_bounds__(1024) void K_rscan1(Dev d) {
     mx = c > mx ? c : mx;
   }
   sum = wave_sum(sum);
-  for (int o = 32; o; o >>= 1) { const int32_t y = __shfl_xor(mx, o, 64); mx = y > mx ? y : mx; }
+  mx = wave_max(mx);
   const int w = threadIdx.x >> 6;
   if (lane() == 0) { s_s[w] = sum; s_m[w] = mx; }
   __syncthreads();
@@ -407,7 +396,7 @@ __global__ __launch_bounds__(1024) void K_rscan1(Dev d) {
 __global__ __launch_bounds__(1024) void K_rscan2(Dev d, int32_t nblk_scan) {
   __shared__ int32_t s_w[16];
   __shared__ int32_t s_pre, s_tot, s_max;
-  const int tid = threadIdx.x, l = lane(), w = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid < 64) {  // blocks before this one, and the totals
     int32_t pre = 0, tot = 0, mx = 0;
     for (int k = tid; k < nblk_scan; k += 64) {
@@ -418,7 +407,7 @@ __global__ __launch_bounds__(1024) void K_rscan2(Dev d, int32_t nblk_scan) {
     }
     pre = wave_sum(pre);
     tot = wave_sum(tot);
-    for (int o = 32; o; o >>= 1) { const int32_t y = __shfl_xor(mx, o, 64); mx = y > mx ? y : mx; }
+    mx = wave_max(mx);
     if (tid == 0) { s_pre = pre; s_tot = tot; s_max = mx; }
   }
   __syncthreads();
@@ -426,11 +415,8 @@ __global__ __launch_bounds__(1024) void K_rscan2(Dev d, int32_t nblk_scan) {
   int32_t c[kScanPer], sum = 0;
 #pragma unroll
   for (int k = 0; k < kScanPer; ++k) { c[k] = g0 + k <= d.G ? d.gcnt[g0 + k] : 0; sum += c[k]; }
-  const int inc = wave_scan_i32(sum);
-  if (l == 63) s_w[w] = inc;
-  __syncthreads();
-  int32_t run = s_pre + inc - sum;
-  for (int k = 0; k < w; ++k) run += s_w[k];
+  int bt;
+  int32_t run = s_pre + block_scan(sum, bt, s_w) - sum;
 #pragma unroll
   for (int k = 0; k < kScanPer; ++k) {
     if (g0 + k <= d.G) d.rsl[g0 + k] = run;  // (K_rstart writes the same values again)
@@ -505,9 +491,8 @@ __global__ __launch_bounds__(256) void K_rstart(Dev d) {
 // step; one workgroup over all gaps took C2 x 8 shards 18 us)
 constexpr int kRunsGB = 1024;
 __global__ __launch_bounds__(kRunsGB) void K_runs(Dev d, uint32_t epoch) {
-  __shared__ int32_t s_w[kRunsGB / 64];
-  __shared__ int64_t s_pre;
-  const int l = lane(), w = threadIdx.x >> 6;
+  __shared__ int32_t s_w[1][kRunsGB / 64];
+  __shared__ int64_t s_pre[1];
   const int64_t b = blockIdx.x;
   const int64_t g = b * kRunsGB + threadIdx.x;
   int32_t tot = 0, below = 0;
@@ -517,23 +502,13 @@ __global__ __launch_bounds__(kRunsGB) void K_runs(Dev d, uint32_t epoch) {
       tot += c;
       below += k < d.shard ? c : 0;
     }
-  const int inc = wave_scan_i32(tot);
-  if (l == 63) s_w[w] = inc;
-  __syncthreads();
-  int32_t wpre = 0, bt = 0;
-  for (int k = 0; k < kRunsGB / 64; ++k) {
-    wpre += k < w ? s_w[k] : 0;
-    bt += s_w[k];
-  }
-  if (w == 0) {
-    int64_t pre;
-    lookback<1>(reinterpret_cast<uint64_t*>(d.bsum), b, (uint64_t)(epoch & 0x3fffffffu) << 32, &bt, &pre,
-                                &d.status[MPC_ST_FLAGS]);
-    if (l == 0) s_pre = pre;
-  }
-  __syncthreads();
+  const int v[1] = {tot};
+  int inc[1], bt[1];
+  int64_t pre[1];
+  chain_scan<kRunsGB / 64, 1>(reinterpret_cast<uint64_t*>(d.bsum), b, epoch, v, inc, bt, pre, s_w, s_pre,
+                              &d.status[MPC_ST_FLAGS]);
   if (g <= d.G) {
-    d.right_start[g] = (int32_t)(s_pre + wpre + inc - tot);
+    d.right_start[g] = (int32_t)(pre[0] + inc[0] - tot);
     d.roff[g] = below;
   }
 }

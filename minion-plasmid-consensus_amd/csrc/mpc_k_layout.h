@@ -90,33 +90,19 @@ __global__ __launch_bounds__(kGB) void K_layout(Dev d, uint32_t epoch) {
     d.rowcnt[g] = rc;
     dv = d.diff[g];
   }
-  const int w = threadIdx.x >> 6, l = lane();
-  const int ir = wave_scan_i32(rc), id = wave_scan_i32(dv);
-  if (l == 63) { s_w[0][w] = ir; s_w[1][w] = id; }
-  __syncthreads();
-  int32_t wr = 0, wd = 0, br = 0, bd = 0;
-  for (int k = 0; k < kGB / 64; ++k) {
-    if (k < w) { wr += s_w[0][k]; wd += s_w[1][k]; }
-    br += s_w[0][k];
-    bd += s_w[1][k];
-  }
-  const uint64_t tag = (uint64_t)(epoch & 0x3fffffffu) << 32;
-  if (w == 0) {  // [2 nb] words: block b's rows word, diff word
-    const int32_t own[2] = {br, bd};
-    int64_t pre[2];
-    lookback<2>(reinterpret_cast<uint64_t*>(d.bsum), b, tag, own, pre, &d.status[MPC_ST_FLAGS]);
-    if (l == 0) { s_pre[0] = pre[0]; s_pre[1] = pre[1]; }
-  }
-  __syncthreads();
-  const int64_t pre_r = s_pre[0], pre_d = s_pre[1];
+  // [2 nb] look-back words: block b's rows word, diff word
+  const int v[2] = {rc, dv};
+  int inc[2], bt[2];
+  int64_t pre[2];
+  chain_scan<kGB / 64, 2>(reinterpret_cast<uint64_t*>(d.bsum), b, epoch, v, inc, bt, pre, s_w, s_pre, &d.status[MPC_ST_FLAGS]);
   if (b == nb - 1 && threadIdx.x == 0) {
-    const int64_t tot = pre_r + br;
+    const int64_t tot = pre[0] + bt[0];
     d.status[MPC_ST_ROWS_NEEDED] = (uint32_t)tot;
     if (tot > d.row_cap) atomicOr(&d.status[MPC_ST_FLAGS], DE_CAP);
   }
   if (g >= d.G) return;
-  const int64_t rb = pre_r + wr + ir - rc;  // exclusive
-  const int64_t dep = pre_d + wd + id;      // inclusive
+  const int64_t rb = pre[0] + inc[0] - rc;  // exclusive
+  const int64_t dep = pre[1] + inc[1];      // inclusive
   d.row_base[g] = (int32_t)rb;
   if (p == 0) d.srow[s] = (int32_t)rb;  // the consensus kernels' sample table (one load, no gbase chain)
   if (rb + rc > d.row_cap) return;      // does not fit: the last block flags DE_CAP (re-plan)

@@ -34,21 +34,17 @@ __device__ __forceinline__ uint64_t wo_sort_key(const WoEv& e) {
 }
 __device__ __forceinline__ int64_t wo_key_read(uint64_t k) { return (int64_t)((k >> 2) & 0x3fffffffu); }
 
-// exclusive scan of x[0, n) in place by one workgroup; returns the total
-__device__ int64_t block_scan_excl(int32_t* x, int64_t n, int32_t* s_w) {
+// exclusive scan of x[0, n) in place by K_woprep's one workgroup; returns the total
+__device__ int64_t block_scan_excl(int32_t* x, int64_t n, int32_t (&s_w)[16]) {
   int64_t carry = 0;
-  const int w = threadIdx.x >> 6, l = lane(), nw = (int)(blockDim.x >> 6);
   for (int64_t b0 = 0; b0 < n; b0 += blockDim.x) {
     const int64_t k = b0 + threadIdx.x;
     const int v = k < n ? x[k] : 0;
-    const int inc = wave_scan_i32(v);
-    if (l == 63) s_w[w] = inc;
-    __syncthreads();
-    int pre = 0, tot = 0;
-    for (int j = 0; j < nw; ++j) { pre += j < w ? s_w[j] : 0; tot += s_w[j]; }
-    if (k < n) x[k] = (int32_t)(carry + pre + inc - v);
+    int tot;
+    const int inc = block_scan(v, tot, s_w);
+    if (k < n) x[k] = (int32_t)(carry + inc - v);
     carry += tot;
-    __syncthreads();
+    __syncthreads();  // s_w: the next pass
   }
   return carry;
 }

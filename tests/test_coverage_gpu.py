@@ -152,6 +152,34 @@ def test_more_records_than_waves(pkg):
     assert np.array_equal(got_rows, rows) and np.array_equal(got_stats, stats)
 
 
+def test_finish_carries_across_its_1024_row_steps(pkg):
+    """K_covfinish sums 1,024 rows per step and carries the sums into the next:
+    targets of 1, 1,024, 1,025 and 2,049 positions, spans and deletions across
+    positions 1,023 / 1,024 and 2,047 / 2,048, the regions' ends on those seams;
+    rows and stats equal the host walk's."""
+    rng = np.random.default_rng(37)
+    lengths, regions = [1, 1024, 1025, 2049], [(0, 1), (0, 1024), (1024, 1025), (1024, 2048)]
+    records = [(0, 0, b":1"), (0, 0, b"*ag"), (0, 1, b"+a")]
+    for s, L in enumerate(lengths[1:], 1):
+        for seam in (m for m in (1024, 2048) if m <= L):
+            for a, cs in ((seam - 3, b":6"), (seam - 5, b":5"), (seam, b":1"), (seam - 1, b"*ag"), (seam, b"*ct"), (seam, b"+ac"),
+                          (seam - 2, b"-acgt"), (seam - 4, b"-acgt"), (seam, b"-a"), (seam - 1, b"-c:1"), (0, b":%d" % seam)):
+                if cu.walk(cs, a, L)[0] == cu.OK:
+                    records += [(s, a, cs)] * 2
+        for _ in range(60):
+            a = int(rng.integers(0, L - 1))
+            records.append((s, a, cu.random_cs(rng, int(rng.integers(1, L - a + 1)), 0.03, 0.03, 0.03)))
+    assert 200 < len(records) < 500
+    cs, off, ts, rs = cu.pack(records)
+    dev = pkg.coverage.run(cs, off, ts, rs, lengths, regions, 40, device=0)
+    host = pkg.coverage.run(cs, off, ts, rs, lengths, regions, 40, device="cpu")
+    assert np.array_equal(dev["rows"], host["rows"]) and np.array_equal(dev["stats"], host["stats"])
+    pos = np.concatenate([[0], np.cumsum(np.asarray(lengths) + 1)])
+    for s, seam in ((1, 1023), (2, 1024), (3, 1024), (3, 2047), (3, 2048)):  # depth and deletions on both sides of a seam
+        assert host["rows"][pos[s] + seam, 0] and host["rows"][pos[s] + seam, 1], (s, seam)
+    assert host["stats"][:, 7].all() and host["stats"][1:, 11].any()
+
+
 @pytest.mark.parametrize("name,rec,code", cu.BAD, ids=[b[0] for b in cu.BAD])
 def test_status_one_bad_record_per_rule(pkg, name, rec, code):
     batch = cu.GOOD + [rec] + cu.GOOD
