@@ -9,6 +9,8 @@ device plumbing the tools share.
                  HIP-runtime rules)
   host           libmpc_ingest.so or the caller's error
   host_check     a host call's return code, or the tool's error with its last_error
+  error_text     the text of a failed libmpc.so call (engine._check, Device.check)
+  h2d            a numpy array's bytes as a uint8 tensor on a GPU (engine.Batch, Device.put)
   Device         the scope of a call into libmpc.so on one GPU: torch, dev, lib,
                  stream, the H2D copies (put, put_all) and the check of its
                  return code
@@ -16,6 +18,7 @@ device plumbing the tools share.
 libmpc_synth.so has no public header: synth.py binds it.
 """
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -121,6 +124,28 @@ def host_check(L, tool, err, rc, accept=()):
     return rc
 
 
+def error_text(L, rc):
+    return f"libmpc error {rc}: {L.mpc_last_error().decode(errors='replace')}"
+
+
+def h2d(torch, dev, a, pad=0, floor=0):
+    """The bytes of a numpy array as a uint8 tensor on ``dev``, ``pad`` zeroed
+    bytes behind them, at least ``floor`` bytes in all: one H2D copy."""
+    a = np.ascontiguousarray(a)
+    size = max(a.nbytes + pad, floor)
+    d = torch.empty(size, dtype=torch.uint8, device=dev)
+    if a.nbytes:
+        # (read-only views of the ingest's buffers are only read here: the
+        # host tensor is the source of one H2D copy, never written)
+        with warnings.catch_warnings():
+            warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+            h = torch.from_numpy(a.reshape(-1).view(np.uint8))
+        (d[: a.nbytes] if size > a.nbytes else d).copy_(h)
+    if pad:
+        d[a.nbytes:].zero_()
+    return d
+
+
 class Device:
     """A call into libmpc.so on GPU ``device``: torch, dev, lib and, once
     entered (torch.cuda.device(dev)), stream: the current stream as the C-ABI
@@ -146,11 +171,7 @@ class Device:
 
     def put(self, a):
         """The bytes of a numpy array as a uint8 tensor on the device."""
-        a = np.ascontiguousarray(a)
-        d = self.torch.empty(a.nbytes, dtype=self.torch.uint8, device=self.dev)
-        if a.nbytes:
-            d.copy_(self.torch.from_numpy(a.reshape(-1).view(np.uint8)))
-        return d
+        return h2d(self.torch, self.dev, a)
 
     def put_all(self, parts):
         """Device pointers of the numpy arrays ``parts``, and the tensor that owns
@@ -167,5 +188,6 @@ class Device:
         of mpc_last_error; every other code raises MpcError."""
         if rc == 0 or rc in accept:
             return rc
-        text = self.lib.mpc_last_error().decode(errors="replace")
-        raise refused(text) if refused is not None and rc == -1 else self._error(f"libmpc error {rc}: {text}")
+        if refused is not None and rc == -1:
+            raise refused(self.lib.mpc_last_error().decode(errors="replace"))
+        raise self._error(error_text(self.lib, rc))

@@ -92,6 +92,10 @@ class LocalExchange:
     def sizes(self, ns):
         return list(ns)
 
+    def shards(self, local):
+        """(numbers of the ``local`` shards this process holds, shards in all)."""
+        return list(range(local)), local
+
 
 class DistExchange:
     """One shard per process over a torch.distributed process group."""
@@ -169,11 +173,10 @@ class DistExchange:
     def _ints(self, xs, op):
         import torch
         dev = "cuda" if self.dist.get_backend(self.group) == "nccl" else "cpu"
+        t = torch.tensor(xs, dtype=torch.int64, device=dev)
         if op == "max":
-            t = torch.tensor(xs, dtype=torch.int64, device=dev)
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
             return [int(t.item())]
-        t = torch.tensor(xs, dtype=torch.int64, device=dev)
         parts = [torch.empty_like(t) for _ in range(self.world)]
         self.dist.all_gather(parts, t, group=self.group)
         return [int(p.item()) for p in parts]
@@ -183,6 +186,10 @@ class DistExchange:
 
     def sizes(self, ns):
         return self._ints(ns, "gather")
+
+    def shards(self, local):
+        assert local == 1, "one shard per process"
+        return [self.rank], self.world
 
 
 def split_samples(samples, n_shards):
@@ -241,16 +248,17 @@ def _wrap_gather(plans, ex, counts):
     return sum(keep)
 
 
-def exchange_step(plans, ex, mdf, gtf, stream=None, used=None, cache=None):
+def exchange_step(plans, ex, mdf, gtf, stream=None, cache=None):
     """One global pileup over the shards in ``plans`` (all of this process's
     shards; with DistExchange exactly one).  Collective: every shard must call it.
-    ``used`` (the runs in use, see below) is a property of the shards' reads:
-    a caller that steps the same batches again passes the value this function
-    returned for them, and the step then has no host synchronisation.  The
-    same holds for the record counts of a batch with negative starts: they are
-    kept in ``cache`` (a dict the caller owns, one per set of batches)."""
+    Returns ``used`` (the runs in use, see below).  It and the record counts of
+    a batch with negative starts are properties of the shards' reads: each is
+    read on the host once and kept in ``cache`` ("used", "wrap": a dict the
+    caller owns, one per set of batches), so a later step over the same batches
+    has no host synchronisation.  Without a cache nothing is kept."""
     import torch
     i32 = torch.int32
+    cache = {} if cache is None else cache
     # negative starts anywhere in the batch (a plan attribute, the same on every
     # shard: the plans were sized from the totals): two more collectives
     wrap = bool(getattr(plans[0], "wrap", False))
@@ -262,12 +270,9 @@ def exchange_step(plans, ex, mdf, gtf, stream=None, used=None, cache=None):
     each("parse")
     ex.reduce([p.buffer(eng.BUF_HASLEFT, i32) for p in plans], "or")
     if wrap:
-        counts = cache.get("wrap") if cache is not None else None
-        if counts is None:
-            counts = wrap_counts(plans, ex)
-            if cache is not None:
-                cache["wrap"] = counts
-        n_wrap = _wrap_gather(plans, ex, counts)
+        if cache.get("wrap") is None:
+            cache["wrap"] = wrap_counts(plans, ex)
+        n_wrap = _wrap_gather(plans, ex, cache["wrap"])
     each("index")
     ex.gather([p.buffer(eng.BUF_RIGHT_CNT, i32) for p in plans], [p.buffer(eng.BUF_RIGHT_CNT_ALL, i32) for p in plans])
     each("runs")
@@ -278,8 +283,10 @@ def exchange_step(plans, ex, mdf, gtf, stream=None, used=None, cache=None):
     # mixed RIGHT events (~35 k there).  One host read of that count (after the
     # gather it is on every shard), then two MAX reductions over the used parts
     # (MAXR and RUN_M are adjacent in the workspace)
-    if used is None:
-        used = int(plans[0].buffer(eng.BUF_MAXR, i32).numel()) + int(plans[0].buffer(eng.BUF_RIGHT_CNT_ALL, i32).sum())
+    if cache.get("used") is None:
+        cache["used"] = (int(plans[0].buffer(eng.BUF_MAXR, i32).numel())
+                         + int(plans[0].buffer(eng.BUF_RIGHT_CNT_ALL, i32).sum()))
+    used = cache["used"]
     heads, tails, parked = [], [], []
     for p in plans:
         span = p.span(eng.BUF_MAXR, eng.BUF_RUN_M, i32)
@@ -325,17 +332,11 @@ class ShardedPileup:
 
     def __init__(self, shards, devices, ex=None, row_cap=None, parse_cus=0):
         self.ex = ex or LocalExchange()
-        local = len(shards)
-        if isinstance(self.ex, DistExchange):
-            assert local == 1, "one shard per process"
-            ranks = [self.ex.rank]
-            n_shards = self.ex.world
-        else:
-            ranks = list(range(local))
-            n_shards = local
-        n_local = [sum(len(s["tstart"]) for s in smp) for smp in shards]
-        n_all = self.ex.sizes(n_local)
-        offs, ng = shard_layout(n_all)
+        ranks, n_shards = self.ex.shards(len(shards))
+        # reads of every sample on every local shard: maps a shard's read index
+        # back to the launch order of one GPU (data_error)
+        self._counts = [[len(s["tstart"]) for s in smp] for smp in shards]
+        offs, ng = shard_layout(self.ex.sizes([sum(c) for c in self._counts]))
         self.batches = [eng.Batch(smp, device=dev, read_offset=offs[r], n_reads_global=ng, shard=r,
                                   n_shards=n_shards, parse_cus=parse_cus) for smp, dev, r in zip(shards, devices, ranks)]
         # negative starts: every shard sizes its plan from the totals over all
@@ -345,25 +346,15 @@ class ShardedPileup:
         neg_cs = sum(self.ex.sizes([b.neg_cs_bytes for b in self.batches]))
         for b in self.batches:
             b.neg_reads, b.neg_cs_bytes = neg, neg_cs
-        # reads of every sample on every local shard: maps a shard's read index
-        # back to the launch order of one GPU (data_error)
-        self._counts = [[len(s["tstart"]) for s in smp] for smp in shards]
         cap = row_cap or max(b.row_estimate() for b in self.batches)
-        cap = self.ex.max_int([cap] * local)[0] if isinstance(self.ex, DistExchange) else cap
+        cap = self.ex.max_int([cap] * len(shards))[0]
         self.plans = [eng.Plan(b, cap) for b in self.batches]
         self._sized = False
-        # runs in use, read back once: valid for THESE batches only -- the
-        # batches are fixed for the object's lifetime (mpc_plan_set_input is
-        # never called on them); rebind() resets it
-        self._used = None
-        self._cache = {}  # record counts of the wrapped odd positions, cached like _used
-
-    def rebind(self):
-        """Forget the cached counts (call after changing any shard's inputs
-        in place): the next step re-reads them."""
-        self._used = None
+        # the once-per-batch host reads of exchange_step (the runs in use, the
+        # record counts of the wrapped odd positions): valid for THESE batches
+        # only -- the batches are fixed for the object's lifetime
+        # (mpc_plan_set_input is never called on them)
         self._cache = {}
-        self._sized = False
 
     # bench.py interface (one local shard)
     @property
@@ -375,26 +366,23 @@ class ShardedPileup:
         return self.plans[0]
 
     def step(self, mdf, gtf, stream=None):
-        # the runs in use depend only on the reads: read back once, reused by
+        # the cached counts depend only on the reads: read back once, reused by
         # later steps over the same batches (no host sync inside a step)
-        used = exchange_step(self.plans, self.ex, mdf, gtf, stream, self._used, self._cache)
+        exchange_step(self.plans, self.ex, mdf, gtf, stream, self._cache)
         if not self._sized:
             # the layout (and so the row count) is identical on every shard
             st = self.plans[0].status()
-            flags = int(st[eng.MPC_ST_FLAGS])
-            flags = self.ex.max_int([flags] * len(self.plans))[0] if isinstance(self.ex, DistExchange) else flags
-            if flags & eng.DE_CAPACITY:
-                need = int(st[eng.MPC_ST_ROWS_NEEDED]) + 16
+            flags = self.ex.max_int([eng.status_error(st)[0]] * len(self.plans))[0]
+            need = eng.replan_rows(st, alone=False, flags=flags)
+            if need:
                 self.plans = [eng.Plan(b, need) for b in self.batches]
-                used = exchange_step(self.plans, self.ex, mdf, gtf, stream, None, self._cache)
+                del self._cache["used"]  # (read again from the new plans; the record counts stay)
+                exchange_step(self.plans, self.ex, mdf, gtf, stream, self._cache)
             self._sized = True
-            self._used = used
 
     def check(self):
         for p in self.plans:
-            st = p.status()
-            if int(st[eng.MPC_ST_FLAGS]):
-                raise eng.DataError(int(st[eng.MPC_ST_FLAGS]), int(st[eng.MPC_ST_FIRST_READ]))
+            p.check()
 
     def data_error(self):
         """(OR of all local shards' MPC_DE_* flags, read index) -- the index
@@ -405,15 +393,11 @@ class ShardedPileup:
         flags, first = 0, None
         totals = [sum(c[s] for c in self._counts) for s in range(len(self._counts[0]))]
         for k, p in enumerate(self.plans):
-            st = p.status()
-            flags |= int(st[eng.MPC_ST_FLAGS])
-            r = int(st[eng.MPC_ST_FIRST_READ])
-            if not int(st[eng.MPC_ST_FLAGS]) or r == 0xFFFFFFFF:
+            f, r = eng.status_error(p.status())
+            flags |= f
+            if not f or r == 0xFFFFFFFF:
                 continue
-            for s, c in enumerate(self._counts[k]):
-                if r < c or s == len(totals) - 1:
-                    break
-                r -= c
+            s, r = eng.locate_read(r, self._counts[k])
             g = sum(totals[:s]) + sum(self._counts[j][s] for j in range(k)) + r
             first = g if first is None else min(first, g)
         return flags, first

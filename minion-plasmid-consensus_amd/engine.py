@@ -5,9 +5,9 @@ single workspace are torch uint8 tensors on the GPU, and the C-ABI receives
 raw device pointers.  There is no CPU fallback: if libmpc.so or a HIP device
 is missing, :class:`Engine` raises.
 """
+import contextlib
 import ctypes
 import os
-import warnings
 
 import numpy as np
 
@@ -32,6 +32,8 @@ DE_NAMES = {DE_OP: "Unknown operator", DE_VALUE: "ValueError", DE_INDEX: "IndexE
 K_PARSE, K_ODD, K_LEFT, K_FLANK, K_INS, K_RSORT = 0, 1, 2, 3, 4, 5
 CS_PAD = 2048  # readable bytes required past the end of the cs buffer (mpc.h)
 FLANK_PAD = 16  # readable bytes required past the end of the up/down buffers (mpc.h)
+PARSE_CHUNKS = 48  # include/mpc.h MPC_PARSE_CHUNKS
+_P64 = ctypes.POINTER(ctypes.c_int64)
 
 
 class MpcError(RuntimeError):
@@ -204,51 +206,90 @@ def set_library(path):
     LIB_PATH = path
 
 
+def status_error(st):
+    """(MPC_DE_* flags, first offending read index) of a plan's status words."""
+    return int(st[MPC_ST_FLAGS]), int(st[MPC_ST_FIRST_READ])
+
+
+def replan_rows(st, alone, flags=None):
+    """The row capacity to plan again with when the status words ``st`` flag
+    rows that did not fit, else None.  The callers differ, and each keeps its
+    question: ``alone=True`` (Runner.step, so pileup too) re-plans when capacity
+    is the ONLY flag; ``alone=False`` (dist.ShardedPileup.step, which passes the
+    ``flags`` its ranks agreed on, and scripts/step_multi.py) whenever it is set."""
+    flags = status_error(st)[0] if flags is None else flags
+    if not flags & DE_CAPACITY or (alone and flags & ~DE_CAPACITY):
+        return None
+    return int(st[MPC_ST_ROWS_NEEDED]) + 16
+
+
+def locate_read(r, counts):
+    """(group, read in it) of read ``r`` of a launch whose groups (a CLI group's jobs, a shard's
+    samples) hold ``counts`` reads, in order.  An index past the end stays with the last group."""
+    for g, c in enumerate(counts):
+        if r < c or g == len(counts) - 1:
+            break
+        r -= c
+    return g, r
+
+
+def _read_begin(reads_per_sample):
+    return np.concatenate([[0], np.cumsum(np.asarray(reads_per_sample, dtype=np.int64))]).astype(np.int64)
+
+
+def _row_estimate(ref_lens):
+    return int((4 * np.asarray(ref_lens, dtype=np.int64) + 8).sum() + 1024)
+
+
+def _host_input(ref_lens, read_begin, cs_bytes, cs_off=None, n_reads_global=None, n_shards=1, **fields):
+    """The host half of mpc_input (include/mpc.h): the counts, the host arrays
+    the planner reads (``cs_off``: h_cs_off, optional) and ``fields`` as given.
+    The struct keeps its numpy arrays alive; Batch.c_input adds the device half."""
+    keep = [np.ascontiguousarray(ref_lens, dtype=np.int64), np.ascontiguousarray(read_begin, dtype=np.int64)]
+    n = int(keep[1][-1])
+    inp = _Input(n_samples=len(keep[0]), h_ref_len=keep[0].ctypes.data_as(_P64),
+                 h_read_begin=keep[1].ctypes.data_as(_P64), n_reads=n, cs_bytes=int(cs_bytes),
+                 n_reads_global=n if n_reads_global is None else n_reads_global, n_shards=n_shards, **fields)
+    if cs_off is not None:
+        keep.append(np.ascontiguousarray(cs_off, dtype=np.int64))
+        inp.h_cs_off = keep[2].ctypes.data_as(_P64)
+    inp._keep = keep
+    return inp
+
+
+@contextlib.contextmanager
+def _host_plan(inp):
+    """The library and the handle of an unbound plan over a _host_input, destroyed on the way out."""
+    L = lib()
+    h = ctypes.c_void_p()
+    _check(L.mpc_plan_create(ctypes.byref(inp), _row_estimate(inp._keep[0]), ctypes.byref(h)))
+    try:
+        yield L, h
+    finally:
+        L.mpc_plan_destroy(h)
+
+
 def geometry(ref_lens, reads_per_sample, cs_bytes, n_reads_global=None, read_offset=0, shard=0, n_shards=1,
              parse_cus=0, neg_reads=0):
     """Host-only planning (no device): the mpc_plan_info a Plan over inputs of
     this shape would use (``parse_cus`` as for Batch; ``neg_reads``: reads with
     a negative tstart).  Needs no GPU."""
-    ref_len = np.ascontiguousarray(ref_lens, dtype=np.int64)
-    counts = np.asarray(reads_per_sample, dtype=np.int64)
-    rb = np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts)]), dtype=np.int64)
-    n = int(rb[-1])
-    inp = _Input(n_samples=len(ref_len), h_ref_len=ref_len.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                 h_read_begin=rb.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_reads=n, cs_bytes=int(cs_bytes),
-                 cs_base=0, read_offset=read_offset, n_reads_global=n_reads_global or n, shard=shard,
-                 n_shards=n_shards, parse_cus=int(parse_cus), neg_reads=int(neg_reads))
-    L = lib()
-    h = ctypes.c_void_p()
-    _check(L.mpc_plan_create(ctypes.byref(inp), int((4 * ref_len + 8).sum() + 1024), ctypes.byref(h)))
-    try:
+    rb = _read_begin(reads_per_sample)
+    inp = _host_input(ref_lens, rb, cs_bytes, read_offset=read_offset, n_reads_global=n_reads_global or int(rb[-1]),
+                      shard=shard, n_shards=n_shards, parse_cus=int(parse_cus), neg_reads=int(neg_reads))
+    with _host_plan(inp) as (L, h):
         info = PlanInfo()
         _check(L.mpc_plan_get_info(h, ctypes.byref(info)))
         return info.as_dict()
-    finally:
-        L.mpc_plan_destroy(h)
-
-
-PARSE_CHUNKS = 48  # include/mpc.h MPC_PARSE_CHUNKS
 
 
 def parse_split(ref_lens, reads_per_sample, cs_off):
     """Host-only (no device): the parse work split a Plan over these reads
     would launch -- (work int32[n_wg, 4] = sample, first read, end read,
     chunks; chunks int32[n_wg, PARSE_CHUNKS + 1] read boundaries)."""
-    ref_len = np.ascontiguousarray(ref_lens, dtype=np.int64)
-    counts = np.asarray(reads_per_sample, dtype=np.int64)
-    rb = np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts)]), dtype=np.int64)
-    off = np.ascontiguousarray(cs_off, dtype=np.int64)
-    n = int(rb[-1])
-    assert off.shape == (n + 1,)
-    p64 = ctypes.POINTER(ctypes.c_int64)
-    inp = _Input(n_samples=len(ref_len), h_ref_len=ref_len.ctypes.data_as(p64), h_read_begin=rb.ctypes.data_as(p64),
-                 n_reads=n, cs_bytes=int(off[-1]), cs_base=0, read_offset=0, n_reads_global=n, shard=0, n_shards=1,
-                 h_cs_off=off.ctypes.data_as(p64))
-    L = lib()
-    h = ctypes.c_void_p()
-    _check(L.mpc_plan_create(ctypes.byref(inp), int((4 * ref_len + 8).sum() + 1024), ctypes.byref(h)))
-    try:
+    rb = _read_begin(reads_per_sample)
+    assert np.shape(cs_off) == (int(rb[-1]) + 1,)
+    with _host_plan(_host_input(ref_lens, rb, cs_off[-1], cs_off)) as (L, h):
         n_wg = L.mpc_plan_parse_tables(h, None, None)
         if n_wg < 0:
             _check(n_wg)
@@ -256,13 +297,11 @@ def parse_split(ref_lens, reads_per_sample, cs_off):
         chunks = np.zeros((n_wg, PARSE_CHUNKS + 1), np.int32)
         _check(L.mpc_plan_parse_tables(h, work.ctypes.data, chunks.ctypes.data) - n_wg)
         return work, chunks
-    finally:
-        L.mpc_plan_destroy(h)
 
 
 def _check(rc):
     if rc != 0:
-        raise MpcError(f"libmpc error {rc}: {lib().mpc_last_error().decode(errors='replace')}")
+        raise MpcError(_native.error_text(lib(), rc))
 
 
 def _torch():
@@ -288,7 +327,7 @@ class Batch:
         self.n_samples = S
         self.ref_len = np.array([len(s["ref"]) for s in samples], dtype=np.int64)
         counts = np.array([len(s["tstart"]) for s in samples], dtype=np.int64)
-        self.read_begin = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.read_begin = _read_begin(counts)
         self.n_reads = int(self.read_begin[-1])
         self.read_offset = int(read_offset)
         self.n_reads_global = int(n_reads_global if n_reads_global is not None else self.n_reads)
@@ -332,20 +371,7 @@ class Batch:
         # all shards before it plans, mpc.h)
         self.aligned_bases = int(sum(int(np.asarray(s.get("aligned", [0])).sum()) for s in samples))
 
-        def dev(a, pad=0):
-            a = np.ascontiguousarray(a)
-            t = torch.empty(max(a.nbytes + pad, 16), dtype=torch.uint8, device=self.device)
-            if a.nbytes:
-                # (read-only views of the ingest's buffers are only read here: the
-                # host tensor is the source of one H2D copy, never written)
-                with warnings.catch_warnings():
-                    warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
-                    h = torch.from_numpy(a.view(np.uint8).reshape(-1))
-                t[: a.nbytes].copy_(h)
-            if pad:
-                t[a.nbytes:].zero_()
-            return t
-
+        dev = lambda a, pad=0: _native.h2d(torch, self.device, a, pad, floor=16)
         self.t = dict(
             ref=dev(ref), ref_off=dev(ref_off), cs=dev(cs, CS_PAD), cs_off=dev(cs_off),
             tstart=dev(tstart.astype(np.int32)), up=dev(up, FLANK_PAD), up_off=dev(up_off),
@@ -357,27 +383,16 @@ class Batch:
                                  (np.diff(dn_off).max() if len(dn_off) > 1 else 0)))
 
     def c_input(self):
-        t = self.t
-        self._keep = (np.ascontiguousarray(self.ref_len), np.ascontiguousarray(self.read_begin),
-                      np.ascontiguousarray(self.h_cs_off, dtype=np.int64))
-        return _Input(
-            ref=t["ref"].data_ptr(), ref_off=t["ref_off"].data_ptr(), cs=t["cs"].data_ptr(),
-            cs_off=t["cs_off"].data_ptr(), tstart=t["tstart"].data_ptr(), up=t["up"].data_ptr(),
-            up_off=t["up_off"].data_ptr(), down=t["down"].data_ptr(), down_off=t["down_off"].data_ptr(),
-            sample=t["sample"].data_ptr(), n_samples=self.n_samples,
-            h_ref_len=self._keep[0].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-            h_read_begin=self._keep[1].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-            n_reads=self.n_reads, cs_bytes=self.cs_bytes, cs_base=0,
-            read_offset=self.read_offset, n_reads_global=self.n_reads_global,
-            shard=self.shard, n_shards=self.n_shards,
-            h_cs_off=(self._keep[2].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if self.balance_bytes
-                      else ctypes.POINTER(ctypes.c_int64)()),
-            parse_cus=int(self.parse_cus), neg_reads=self.neg_reads, neg_cs_bytes=self.neg_cs_bytes,
-        )
+        inp = _host_input(self.ref_len, self.read_begin, self.cs_bytes, self.h_cs_off if self.balance_bytes else None,
+                          read_offset=self.read_offset, n_reads_global=self.n_reads_global, shard=self.shard,
+                          n_shards=self.n_shards, parse_cus=self.parse_cus, neg_reads=self.neg_reads,
+                          neg_cs_bytes=self.neg_cs_bytes)
+        for name, t in self.t.items():  # the device half: self.t is keyed by mpc_input's pointer fields
+            setattr(inp, name, t.data_ptr())
+        return inp
 
     def row_estimate(self):
-        n = self.ref_len
-        return int((4 * n + 8).sum() + 4 * self.max_flank * self.n_samples + 1024)
+        return _row_estimate(self.ref_len) + 4 * self.max_flank * self.n_samples
 
 
 class Plan:
@@ -417,29 +432,17 @@ class Plan:
 
     def buffer(self, which, dtype):
         """View of one workspace buffer (memoized: the binding never moves)."""
-        key = ("b", which, dtype)
-        v = self._views.get(key)
-        if v is None:
-            v = self._views[key] = self._buffer(which, dtype)
-        return v
-
-    def _buffer(self, which, dtype):
-        torch = _torch()
-        off, cnt = ctypes.c_size_t(), ctypes.c_int64()
-        _check(lib().mpc_plan_buffer(self.h, which, ctypes.byref(off), ctypes.byref(cnt)))
-        item = torch.empty(0, dtype=dtype).element_size()
-        return self.ws[off.value: off.value + cnt.value * item].view(dtype)
+        v = self._views.get((which, which, dtype))
+        return self._view(which, which, dtype) if v is None else v
 
     def span(self, first, last, dtype):
         """The workspace bytes from buffer ``first`` through buffer ``last``
         (include/mpc.h: buffers exchanged together are laid out in order)."""
-        key = ("s", first, last, dtype)
-        v = self._views.get(key)
-        if v is None:
-            v = self._views[key] = self._span(first, last, dtype)
-        return v
+        v = self._views.get((first, last, dtype))
+        return self._view(first, last, dtype) if v is None else v
 
-    def _span(self, first, last, dtype):
+    def _view(self, first, last, dtype):
+        """Makes and keeps span()'s view; a buffer is the span from itself to itself."""
         torch = _torch()
         o0, c0, o1, c1 = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_size_t(), ctypes.c_int64()
         _check(lib().mpc_plan_buffer(self.h, first, ctypes.byref(o0), ctypes.byref(c0)))
@@ -448,7 +451,8 @@ class Plan:
         end = o1.value + c1.value * item
         if o1.value < o0.value or (end - o0.value) % item:
             raise MpcError("buffers %d..%d are not an ordered span" % (first, last))
-        return self.ws[o0.value: end].view(dtype)
+        v = self._views[first, last, dtype] = self.ws[o0.value: end].view(dtype)
+        return v
 
     def stream_ptr(self, stream=None):
         torch = _torch()
@@ -472,14 +476,16 @@ class Plan:
         torch = _torch()
         return self.buffer(BUF_STATUS, torch.int32).cpu().numpy().view(np.uint32)
 
-    def fetch(self):
-        """Copy the calls of every sample to the host.  Raises DataError when
-        the reference would have failed on this input."""
-        torch = _torch()
-        st = self.status()
-        flags = int(st[MPC_ST_FLAGS])
+    def check(self):
+        """Raises DataError when the reference would have failed on this input."""
+        flags, read = status_error(self.status())
         if flags:
-            raise DataError(flags, int(st[MPC_ST_FIRST_READ]))
+            raise DataError(flags, read)
+
+    def fetch(self):
+        """Copy the calls of every sample to the host, after check()."""
+        torch = _torch()
+        self.check()
         nc = self.buffer(BUF_NCALLS, torch.int32).cpu().numpy()
         total = int(nc[-1])
         calls = self.buffer(BUF_CALLS, torch.int32)[: total * 4].cpu().numpy().view(np.uint32).reshape(-1, 4)
@@ -498,19 +504,11 @@ class Plan:
 
 def pileup(samples, mdf, gtf, device=0, row_cap=None):
     """One-shot helper: samples (packed dicts) -> per-sample call dicts.
-    Re-plans once if the row capacity estimate was too small."""
-    torch = _torch()
-    batch = Batch(samples, device=device)
-    plan = Plan(batch, row_cap)
-    plan.run(mdf, gtf)
-    st = plan.status()
-    flags = int(st[MPC_ST_FLAGS])
-    if flags & DE_CAPACITY and not (flags & ~DE_CAPACITY):
-        need = int(st[MPC_ST_ROWS_NEEDED])
-        plan = Plan(batch, need + 16)
-        plan.run(mdf, gtf)
-    res = plan.fetch()
-    torch.cuda.synchronize(batch.device)
+    Re-plans once if the row capacity estimate was too small (Runner.step)."""
+    runner = Runner(samples, device, row_cap)
+    runner.step(mdf, gtf)
+    res = runner.fetch()
+    _torch().cuda.synchronize(runner.batch.device)
     return res
 
 
@@ -526,17 +524,14 @@ class Runner:
     def step(self, mdf, gtf, stream=None):
         self.plan.run(mdf, gtf, stream)
         if not self._sized:
-            st = self.plan.status()
-            flags = int(st[MPC_ST_FLAGS])
-            if flags & DE_CAPACITY and not (flags & ~DE_CAPACITY):
-                self.plan = Plan(self.batch, int(st[MPC_ST_ROWS_NEEDED]) + 16)
+            need = replan_rows(self.plan.status(), alone=True)
+            if need:
+                self.plan = Plan(self.batch, need)
                 self.plan.run(mdf, gtf, stream)
             self._sized = True
 
     def check(self):
-        st = self.plan.status()
-        if int(st[MPC_ST_FLAGS]):
-            raise DataError(int(st[MPC_ST_FLAGS]), int(st[MPC_ST_FIRST_READ]))
+        self.plan.check()
 
     def fetch(self):
         return self.plan.fetch()

@@ -138,11 +138,8 @@ def _ingest_and_pileup(ingest, engine, jobs, args, tm):
             except engine.DataError as e:
                 # the group's samples are its jobs in idx order: map the launch's
                 # read index back to (job, read in the job)
-                r = e.read
-                for k, j in enumerate(idx):
-                    if r < n_of[j] or k == len(idx) - 1:
-                        break
-                    r -= n_of[j]
+                k, r = engine.locate_read(e.read, [n_of[j] for j in idx])
+                j = idx[k]
                 if first is None or j < first[0]:
                     first = (j, r, e.flags)
                 continue

@@ -49,9 +49,9 @@ for r in range(rounds):
         eng.LIB_PATH = p
         plan = eng.Plan(batch)
         plan.run(0.1, 5.0)
-        st_ = plan.status()
-        if int(st_[eng.MPC_ST_FLAGS]) & eng.DE_CAPACITY:
-            plan = eng.Plan(batch, int(st_[eng.MPC_ST_ROWS_NEEDED]) + 16)
+        need = eng.replan_rows(plan.status(), alone=False)
+        if need:
+            plan = eng.Plan(batch, need)
         for _ in range(2):
             plan.run(0.1, 5.0)
         torch.cuda.synchronize()

@@ -146,3 +146,53 @@ def test_records_past_the_list_bound_are_dropped():
     assert int(plans[0].buf[eng.BUF_WRAP_ALL][0]) == 2 * (CAP - 2)
     assert plans[0].buf[eng.BUF_WRAP_ALL].numel() == (CAP + 1) * W
     assert np.array_equal(plans[0].buf[eng.BUF_WRAP_ALL].numpy(), plans[1].buf[eng.BUF_WRAP_ALL].numpy())
+
+
+def _status(eng, flags, rows_needed=1000):
+    st = np.zeros(8, np.uint32)
+    st[eng.MPC_ST_FLAGS], st[eng.MPC_ST_ROWS_NEEDED], st[eng.MPC_ST_FIRST_READ] = flags, rows_needed, 0xFFFFFFFF
+    return st
+
+
+def test_replan_rows_two_conditions():
+    """engine.replan_rows: the rows needed + 16 when the capacity flag asks for
+    a re-plan; "alone" (one GPU) only when no other flag is set, "any" (the
+    sharded step) whenever the capacity bit is."""
+    _, eng = _mod()
+    cap, key = eng.DE_CAPACITY, eng.DE_KEY
+    for flags, alone, any_ in ((0, None, None), (cap, 1016, 1016), (cap | key, None, 1016), (key, None, None)):
+        assert eng.replan_rows(_status(eng, flags), alone=True) == alone, flags
+        assert eng.replan_rows(_status(eng, flags), alone=False) == any_, flags
+    # the flags the ranks agreed on decide, the rows come from the status words
+    assert eng.replan_rows(_status(eng, 0, 77), alone=False, flags=cap) == 93
+    assert eng.replan_rows(_status(eng, cap), alone=False, flags=0) is None
+
+
+def test_locate_read():
+    _, eng = _mod()
+    # 3: the empty group is skipped; 9: past the end, the last group takes it
+    for r, exp in ((0, (0, 0)), (2, (0, 2)), (3, (2, 0)), (6, (2, 3)), (9, (2, 6))):
+        assert eng.locate_read(r, [3, 0, 4]) == exp, r
+    for r in (0, 4, 5, 1000):
+        assert eng.locate_read(r, [5]) == (0, r)
+
+
+def test_used_is_cached_with_the_record_counts():
+    """The runs in use are read once per set of batches: a step with a cache
+    leaves them in cache["used"], and the next step does not read them again
+    (RIGHT_CNT_ALL poisoned in between: a second read would change the lengths
+    of the MAX reductions)."""
+    dist, eng = _mod()
+    plans = [tdc.FakePlan(k, 3, 3 * G) for k in range(3)]
+    ex, cache = Counting(), {}
+    used = dist.exchange_step(plans, ex, 0.1, 5.0, cache=cache)
+    assert used == tdc.expected(3, 3 * G)[2] and cache == {"used": used}
+    first = list(ex.ops)
+    for p in plans:  # (RIGHT_CNT too: the step's own gather rewrites RIGHT_CNT_ALL from it)
+        p.buf[eng.BUF_RIGHT_CNT_ALL].fill_(1000)
+        p.buf[eng.BUF_RIGHT_CNT].fill_(1000)
+    assert dist.exchange_step(plans, ex, 0.1, 5.0, cache=cache) == used and cache == {"used": used}
+    assert ex.ops[len(first):] == first
+    assert int(plans[0].buf[eng.BUF_RIGHT_CNT_ALL].sum()) == 1000 * 3 * G  # (the poison was there when "used" was due)
+    # without a cache nothing is kept: the poisoned counts are read
+    assert dist.exchange_step(plans, ex, 0.1, 5.0) == G + 1000 * 3 * G

@@ -214,3 +214,65 @@ def test_error_index_is_the_one_gpu_index(pkg):
     with pytest.raises(eng.DataError) as two:
         dist.pileup_sharded([other, smp], -1.0, 1.0, [0, 0])
     assert (two.value.flags, two.value.read) == (one.value.flags, one.value.read)
+
+
+@pytest.fixture(scope="module")
+def small_case(pkg):
+    """(sample, oracle calls, engine.pileup's calls) at (0.1, 5.0): 240 bases,
+    400 reads with insertions and negative starts; computed once, never changed."""
+    smp = neg_util.neg_sample(5, n_reads=400)
+    return smp, du.oracle_one(smp, 0.1, 5.0), pkg.engine.pileup([smp], 0.1, 5.0)[0]
+
+
+def test_sharded_replan_from_a_small_row_cap(pkg, small_case):
+    """Three shards planned with 10 rows: the first step re-plans every shard
+    with the rows needed + 16 and runs again (the record counts of the wrapped
+    positions are kept, the runs in use read again), and gives the calls of
+    one GPU and of the oracle; so does a second step, on the same plans."""
+    dist, eng = _dist(), pkg.engine
+    smp, exp, one = small_case
+    sp = dist.ShardedPileup(dist.split_samples([smp], 3), [0] * 3, row_cap=10)
+    assert [p.row_cap for p in sp.plans] == [10] * 3 and all(p.wrap for p in sp.plans)
+    sp.step(0.1, 5.0)
+    sized = sp.plans
+    need = [int(p.status()[eng.MPC_ST_ROWS_NEEDED]) for p in sized]
+    print("rows needed", need, "row_cap", [p.row_cap for p in sized])
+    assert need[0] > 10 and need == [need[0]] * 3
+    assert [p.row_cap for p in sized] == [need[0] + 16] * 3
+    assert len(sp._cache["wrap"]) == 3
+    for step in range(2):
+        if step:
+            sp.step(0.1, 5.0)
+        sp.check()
+        assert sp.data_error() == (0, None) and sp.plans is sized
+        got = sp.fetch()[0]
+        du.compare(got, exp, ("replan oracle", step))
+        du.compare(got, one, ("replan one GPU", step))
+        assert np.array_equal(got["raw"], one["raw"])
+
+
+# (flags, read index) with 10 rows planned and read 137 of 200 inserting a base
+# outside ACGT, as the code before the capacity rule was stated once reported
+# them.  One GPU re-plans only when capacity is the only flag, so the error is
+# raised from the 10-row run with the capacity bit still set; the sharded step
+# re-plans whenever the capacity bit is set and reports from the sized run.
+ONE_GPU_ERROR = (16 | 8, 137)  # MPC_DE_CAPACITY | MPC_DE_KEY
+SHARDED_ERROR = (8, 137)  # MPC_DE_KEY
+
+
+def test_small_row_cap_with_a_rejected_read_one_gpu(pkg):
+    eng = pkg.engine
+    with pytest.raises(eng.DataError) as err:
+        eng.pileup([_plain_sample(200, 137)], -1.0, 1.0, row_cap=10)
+    print("one GPU", (err.value.flags, err.value.read))
+    assert (err.value.flags, err.value.read) == ONE_GPU_ERROR
+
+
+def test_small_row_cap_with_a_rejected_read_three_shards(pkg):
+    dist, eng = _dist(), pkg.engine
+    sp = dist.ShardedPileup(dist.split_samples([_plain_sample(200, 137)], 3), [0] * 3, row_cap=10)
+    sp.step(-1.0, 1.0)
+    print("three shards", sp.data_error(), [p.row_cap for p in sp.plans])
+    assert sp.data_error() == SHARDED_ERROR
+    with pytest.raises(eng.DataError):
+        sp.check()
