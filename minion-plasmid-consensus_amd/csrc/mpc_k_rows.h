@@ -102,10 +102,13 @@ __global__ __launch_bounds__(kUB) void K_ins(InsArgs a) {
 // flank bytes are contiguous, so the wave stages them in its LDS with 16-byte
 // loads (both sides before any tally) and walks them in 256-byte segments,
 // consecutive lanes on consecutive bytes.  The owner of a byte needs no block
-// barrier: the lane of a flank starting in the segment marks its start byte
-// in the wave's LDS row, and a max-scan over the segment (a byte's owner is
-// the last flank starting at or before it) gives every byte its flank's lane,
-// whose row offset one ds_bpermute fetches.  Rows of the hot gaps (voted per
+// barrier and no scan: a wave's non-empty flanks lie one after the other in
+// lane order, so the owner of byte x is the k-th of them, k = the flank starts
+// at or before x.  Per stage every such flank sets the bit of its start byte
+// in the wave's LDS bitmap (one ds_or); per 64-byte group a ballot of the
+// lanes' bits and a lane prefix count give k (a scalar popcount carries it
+// over groups, segments and stages), and a table written once per side holds
+// the k-th flank's row offset.  Rows of the hot gaps (voted per
 // chunk of reads: for full-length reads gap 0 upstream, gap n downstream) are
 // tallied in LDS windows, everything else with global atomics.  Block
 // barriers: two per chunk (after its records load, which hands the vote the
@@ -122,6 +125,8 @@ constexpr int kFSeg = 256;      // flank bytes per wave step (4 per lane)
 constexpr int kFStageLd = 2;    // 16-byte loads per lane per staged side (2 KiB per wave)
 constexpr int kFStageBytes = kFStageLd * 64 * 16;  // the stage itself
 constexpr int kFStage = kFStageBytes - 16;  // flank bytes per side staged per wave (C3: 64 reads x 0-40 B, mean 1280)
+constexpr int kFBitmap = kFStageBytes / 32;  // dwords of a wave's start bitmap: one bit per staged byte
+static_assert(kFBitmap == 64, "one bitmap word per lane");
 // K_flank blocks at most (two per CU): beyond, a block takes a contiguous range of
 // chunks (C3: 1954 one-chunk blocks 135 us, 512 blocks of ~4 chunks 110 us)
 #ifndef MPC_FLANK_BLOCKS_MAX
@@ -159,7 +164,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
   // row r, code c at word 5 r + c: consecutive rows (the bytes of one flank,
   // on consecutive lanes) fall on distinct banks
   __shared__ uint32_t win[2][kWinRows * 5];
-  __shared__ __attribute__((aligned(16))) uint32_t own[NW][kFSeg];  // per wave: 1 + lane of the flank starting at each byte
+  __shared__ uint32_t bm[NW][kFBitmap];  // per wave: one bit per staged byte, set where a non-empty flank starts
+  __shared__ int32_t rkt[NW][64];        // per wave and side: the row offset of the k-th non-empty flank
   __shared__ __attribute__((aligned(16))) uint8_t stg[NW][2][kFStageBytes];  // per wave and side: staged flank bytes
   // the windows' first rows: placed, and voted for the chunk (by chunk parity: a
   // wave still comparing chunk k's vote never sees chunk k + 1's)
@@ -190,7 +196,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
   };
   uint32_t lerr = 0;
   int64_t lread = INT64_MAX;
-  uint32_t* ow_w = own[w];
+  uint32_t* bm_w = bm[w];
+  int32_t* rk_w = rkt[w];
 #pragma unroll 1
   for (int64_t ck = ck0; ck < ck1; ++ck) {
     const int64_t rb = ck * RB + (int64_t)w * 64;  // the wave's first read
@@ -306,8 +313,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
       uint32_t* wn = win[side];
       uint8_t* st = stg[w][side];
       if (nb >= (1 << 30)) {  // (huge flanks: every lane walks its own from HBM; rows < 2^31)
-        const int64_t fo = live ? (side ? a.down_off[r] : a.up_off[r]) : 0;
-        const int64_t fl = live ? (side ? a.down_off[r + 1] : a.up_off[r + 1]) - fo : 0;
+        int64_t fo = live ? (side ? a.down_off[r] : a.up_off[r]) : 0;
+        int64_t fl = live ? (side ? a.down_off[r + 1] : a.up_off[r + 1]) - fo : 0;
+        // (a use of both on every path from here: when a branch around the
+        // loads' first use left them pending, the compiler waited for them --
+        // vmcnt(0), so for every global atomic before it -- at the next write of
+        // their registers, in each iteration of the segment loop below)
+        asm volatile("" : "+v"(fo), "+v"(fl));
         for (int64_t j = 0; frs >= 0 && j < fl; ++j) {
           const int code = code_exact(src[fo + j]);
           if (code < 0) { lerr |= DE_KEY; lread = r < lread ? r : lread; continue; }
@@ -323,7 +335,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
       const int32_t rowoff = (live && frs >= 0) ? frs - xo : INT32_MIN;
       const bool ne = live && L > 0;
       const int nb32 = (int)nb;
-      int carry = 0;  // owner (1 + lane) of the previous byte group's last byte
+      // the side's non-empty flanks by rank (their order on the lanes): the
+      // row offset of the k-th one at rk_w[k].  (The previous side's and
+      // chunk's reads of the table are behind: LDS works a wave's
+      // instructions in order.)
+      const uint64_t nem = ballot(ne);
+      if (ne) rk_w[lanes_below(nem)] = rowoff;
+      uint32_t carry = 0;  // flanks starting before the byte group: the rank of its predecessor's owner
 #pragma unroll 1
       for (int c0 = 0; c0 < nb32; c0 += kFStage) {
         if (c0 > 0) {  // (a wave with more than kFStage bytes on this side)
@@ -331,70 +349,70 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MULTI |
           stage_load(src, Bw, nb, c0, v);
           stage_store(st, v);
         }
-        wave_sync_lds();
         const int sh = (int)((Bw + c0) & 15);
         const int c1 = nb32 - c0 < kFStage ? nb32 : c0 + kFStage;
+        // the stage's start bitmap: bit x - c0 is set where a non-empty flank
+        // starts on byte x (distinct bytes: one ds_or per flank, no return).
+        // Only starts in this stage: the others count when their stage comes
+        bm_w[l] = 0;
+        if (ne && xo >= c0 && xo < c1) atomicOr(bm_w + ((xo - c0) >> 5), 1u << ((xo - c0) & 31));
+        wave_sync_lds();
 #pragma unroll 1
         for (int S = c0; S < c1; S += kFSeg) {
           // lane l takes bytes S + 64 k + l (k < 4): consecutive lanes on
           // consecutive bytes, so a flank's bytes (consecutive rows) leave as few
           // 64-B atomic requests as they can (4 bytes per lane put every lane's
           // row atomic in a segment of its own: C3 K_flank +30 %)
-          *reinterpret_cast<uint4*>(ow_w + 4 * l) = make_uint4(0u, 0u, 0u, 0u);
-          wave_sync_lds();
-          // non-empty flanks start on distinct bytes; only starts in this
-          // stage (< c1): a later one would enter the carry into the next
-          // stage ahead of the bytes before it
-          if (ne && xo >= S && xo < S + kFSeg && xo < c1) ow_w[xo - S] = (uint32_t)(l + 1);
-          wave_sync_lds();
           // The four 64-byte groups of the segment go through each step
-          // TOGETHER: their marks and staged bytes in one batch of LDS reads,
-          // four independent scans (only the scalar carry links the groups),
-          // one batch of ds_bpermute -- two LDS round trips per segment before
-          // the tallies; group after group it was three per group, each
-          // waiting for the previous group's LDS adds as well (LDS completes
-          // in order).  The byte reads are unconditional, so their index stays
-          // inside the stage: only group 3 of a full stage's last segment can
-          // pass it (dead lanes, x >= c1)
+          // TOGETHER: their bitmap words and staged bytes in one batch of LDS
+          // reads, four ranks (only the scalar carry links the groups), one
+          // batch of table reads -- two LDS round trips per segment before
+          // the tallies, nothing written per segment.  The byte reads are
+          // unconditional, so their index stays inside the stage: only group
+          // 3 of a full stage's last segment can pass it (dead lanes, x >= c1)
           static_assert(15 + (kFStage - 1) / kFSeg * kFSeg + 191 < kFStageBytes, "groups 0-2 read inside the stage");
+          static_assert((kFStage - 1) / kFSeg * kFSeg + kFSeg <= 64 * 32, "a stage's segments stay inside the bitmap");
           const int bx = sh + (S - c0) + l;
-          int o[4];
-          uint32_t ch[4];
+          const uint32_t* bm_s = bm_w + ((S - c0) >> 5) + (l >> 5);  // the word of byte S + l; group k: + 2 k
+          uint32_t bw[4], ch[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) o[k] = (int)ow_w[64 * k + l];
+          for (int k = 0; k < 4; ++k) bw[k] = bm_s[2 * k];
 #pragma unroll
           for (int k = 0; k < 4; ++k) ch[k] = st[k < 3 ? bx + 64 * k : min(bx + 192, kFStageBytes - 1)];
           // (all eight are in registers here: none sinks to its use below)
-          asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(ch[0]), "+v"(ch[1]), "+v"(ch[2]), "+v"(ch[3]));
-#pragma unroll
-          for (int k = 0; k < 4; ++k) o[k] = wave_scan_max_i32(o[k]);
+          asm volatile("" : "+v"(bw[0]), "+v"(bw[1]), "+v"(bw[2]), "+v"(bw[3]), "+v"(ch[0]), "+v"(ch[1]), "+v"(ch[2]), "+v"(ch[3]));
+          uint32_t rk[4];  // the rank of the byte's owner: flanks starting at or before it (0: none)
           int32_t q[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const int top = wave_last_i32(o[k]);
-            o[k] = max(o[k], carry);  // owner (1 + lane) of byte S + 64 k + l; 0: past the wave's range
-            carry = max(top, carry);  // (= the owner on lane 63: a scalar max, no lane read of the sum)
+            const uint32_t mine = (bw[k] >> (l & 31)) & 1u;
+            const uint64_t m = ballot(mine != 0);  // the group's starts
+            rk[k] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, carry + mine));
+            carry += (uint32_t)__popcll(m);
             // the row offset of the byte's flank
-            q[k] = __builtin_amdgcn_ds_bpermute(4 * max(o[k] - 1, 0), rowoff);
+            q[k] = rk_w[rk[k] > 0 ? rk[k] - 1 : 0];
           }
           asm volatile("" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]));
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const int x = S + 64 * k + l;
-            const int inc = o[k];
-            if (x >= c1 || inc == 0) continue;
-            const int32_t row = x + q[k];
-            if (row < 0) continue;  // flank without a row
-            const int code = code_exact(ch[k]);
-            if (code < 0) {
-              lerr |= DE_KEY;
-              const int64_t rr = rb + inc - 1;
-              lread = rr < lread ? rr : lread;
-              continue;
+            int32_t row = x + q[k];
+            if (x >= c1 || rk[k] == 0) row = -1;  // past the wave's range
+            int code = -1;
+            if (row >= 0) {  // (< 0: also a flank without a row)
+              code = code_exact(ch[k]);
+              if (code < 0) {
+                lerr |= DE_KEY;
+                uint64_t m = nem;  // the lane of the rk-th non-empty flank
+                for (uint32_t i = 1; i < rk[k]; ++i) m &= m - 1;
+                const int64_t rr = rb + __builtin_ctzll(m);
+                lread = rr < lread ? rr : lread;
+              }
             }
             const uint32_t wr = (uint32_t)(row - w032);
-            if (wr < (uint32_t)kWinRows) atomicAdd(wn + wr * 5 + code, 1u);
-            else atomicAdd(a.rows + (int64_t)row * 4 + code, 1u);
+            const bool hit = wr < (uint32_t)kWinRows;
+            if (code >= 0 && hit) atomicAdd(wn + wr * 5 + code, 1u);
+            if (code >= 0 && !hit) atomicAdd(a.rows + (int64_t)row * 4 + code, 1u);
           }
         }
         wave_sync_lds();  // (the stage is reloaded for the next kFStage bytes)
