@@ -60,7 +60,8 @@
  * 0 <= b < W = 2 d + 1; cells with j < 0 or j > n are infinite; the value at
  * (m, end) must be d, else the read's status is MPC_ALIGN_BAD_SCAN.
  *
- * mpc_align_revcomp and mpc_align_trace live in libmpc.so (HIP, gfx950; errors
+ * mpc_align_revcomp, mpc_align_trace, mpc_align_cs_sizes and mpc_align_cs_write
+ * live in libmpc.so (HIP, gfx950; errors
  * through mpc_last_error of mpc.h); everything else lives in libmpc_ingest.so
  * (host only; errors through mpc_align_last_error).  All return 0 or a
  * negative code (the MPC_E_* values of mpc.h).
@@ -104,7 +105,58 @@ int mpc_align_revcomp(uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_tab, i
 int mpc_align_trace(const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_jobs, int32_t n_jobs, uint8_t* d_flags,
                     int64_t flags_bytes, int32_t* d_out, int32_t* d_runs, int64_t runs_cap, void* stream);
 
+/* ---- the handoff to the pileup (reads_consensus; DESIGN.md "reads_consensus") --
+ * What mpc_input (mpc.h) wants of a traced read, built from its job, out row
+ * and runs without the PAF text in between.  With the end rule above (a / b
+ * the dropped leading / trailing read bases, a_t / b_t the dropped leading /
+ * trailing target bases):
+ *   kept    0 for a read with no '=' run: no PAF line, no pileup read
+ *   tstart  start + a_t;  tend = end - b_t
+ *   cs      "Z:" followed by the cs string of the PAF line
+ *   up      oriented read [0, a), upper-cased;  down  oriented read [m - b, m)
+ * size row   int64[8] per read  {kept, cs_len, up_len, down_len, tstart, tend,
+ *            n_eq, n_ops} (cs_len counts the "Z:"; all 0 when not kept)
+ * place row  int64[3] per read  {cs_off, up_off, down_off}: where the read's
+ *            bytes go in the three output buffers; ascending in job order,
+ *            disjoint, inside the buffers (a read that is not kept owns none)
+ * status     int32 per read: MPC_ALIGN_OK, or MPC_ALIGN_BAD_JOB for a read the
+ *            kernel refused (nothing of it was written)
+ */
+
+/* K_acslen: the size rows of n_jobs traced reads (the device tensors of one
+ * mpc_align_trace launch), one wave64 per read.  The job table and the out rows
+ * are read back and checked on the host before the launch (the job rule, the
+ * trace output inside its bounds); after it the call waits for the stream and
+ * refuses, naming the read, a read whose runs do not walk exactly its m read
+ * bases and its target span (its row: kept = -1). */
+int mpc_align_cs_sizes(const int64_t* d_jobs, int32_t n_jobs, int64_t seq_bytes, const int32_t* d_out,
+                       const int32_t* d_runs, int64_t runs_cap, int64_t* d_sizes, void* stream);
+
+/* K_acswrite: cs, up and down of every kept read at its place, one wave64 per
+ * read.  Jobs, out rows, size rows and places are read back and checked on the
+ * host before the launch (places ascending, disjoint and inside cs_bytes /
+ * up_bytes / down_bytes; run spans inside runs_cap).  The kernel measures the
+ * read again and writes only when that gives the size row it was handed; after
+ * the launch the call waits, reads d_status and refuses a read with a status.
+ * No byte outside the reads' own slots is written. */
+int mpc_align_cs_write(const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_jobs, int32_t n_jobs,
+                       const int32_t* d_out, const int32_t* d_runs, int64_t runs_cap, const int64_t* d_sizes,
+                       const int64_t* d_place, uint8_t* d_cs, int64_t cs_bytes, uint8_t* d_up, int64_t up_bytes,
+                       uint8_t* d_down, int64_t down_bytes, int32_t* d_status, void* stream);
+
 /* ---- host (libmpc_ingest.so) ----------------------------------------------- */
+
+/* The host twins of the two calls above, same tables, reads spread over
+ * `threads` host threads: the checker of the kernels and the sanitizer target.
+ * Both check every read first (job rule, trace output, the runs' walk; the
+ * writer also that each size row is the one the runs give, and the places) and
+ * write nothing when one is refused. */
+int mpc_align_cs_sizes_host(const int64_t* jobs, int32_t n_jobs, int64_t seq_bytes, const int32_t* out,
+                            const int32_t* runs, int64_t runs_cap, int64_t* sizes, int threads);
+int mpc_align_cs_write_host(const uint8_t* seq, int64_t seq_bytes, const int64_t* jobs, int32_t n_jobs,
+                            const int32_t* out, const int32_t* runs, int64_t runs_cap, const int64_t* sizes,
+                            const int64_t* place, uint8_t* cs, int64_t cs_bytes, uint8_t* up, int64_t up_bytes,
+                            uint8_t* down, int64_t down_bytes, int threads);
 
 /* The reverse complements on the host (--device cpu), same table. */
 int mpc_align_revcomp_host(uint8_t* seq, int64_t seq_bytes, const int64_t* tab, int32_t n_reads, int threads);

@@ -2,12 +2,12 @@
 the repo snapshot to the GPU box).
 
   libmpc.so        HIP kernels + C-ABI (include/mpc.h, mpc_verify.h: K_vscan, mpc_coverage.h: K_covparse, mpc_linkage.h: K_lnkparse,
-                   mpc_align.h: K_arevcomp, K_atrace, mpc_draft.h: K_dvote, K_dcall), hipcc --offload-arch=gfx950;
+                   mpc_align.h: K_arevcomp, K_atrace, K_acslen, K_acswrite, mpc_draft.h: K_dvote, K_dcall), hipcc --offload-arch=gfx950;
                    its host planner (csrc/mpc_plan.cpp) with g++
   libmpc_synth.so  host-only synthetic data generator (g++)
   libmpc_ingest.so native host I/O: ingest (Steps 1-3) and writers (Step 7) (include/mpc_ingest.h, g++ -pthread)
                    and the host halves of verify_consensus (include/mpc_verify.h), coverage_qc (mpc_coverage.h)
-                   linkage_qc (mpc_linkage.h), align_reads (mpc_align.h) and draft_assembly (mpc_draft.h)
+                   linkage_qc (mpc_linkage.h), align_reads and the handoff of reads_consensus (mpc_align.h) and draft_assembly (mpc_draft.h)
 
 Shared glue, listed below so that a change to it makes its library stale:
 csrc/mpc_launch.h (the launchers of the tool .hip files) in HIP_HEADERS,

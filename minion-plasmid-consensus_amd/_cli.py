@@ -61,6 +61,25 @@ def device_arg(text):
         raise argparse.ArgumentTypeError("a HIP device index or 'cpu'")
 
 
+def gpu_arg(text):
+    """--device of a tool with no host path."""
+    try:
+        return int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("a HIP device index (there is no 'cpu': the pileup has no host path)")
+
+
+def fraction_arg(text):
+    """--max-error: a number >= 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = -1.0
+    if not v >= 0:
+        raise argparse.ArgumentTypeError("a number >= 0")
+    return v
+
+
 def region_arg(text):
     try:
         lo, hi = (int(x) for x in text.split(":"))

@@ -54,6 +54,8 @@ def device_prototypes():
         "mpc_linkage_scratch_bytes": (i64, [i64, i32]),
         "mpc_align_revcomp": (i32, [vp, i64, vp, i32, vp]),
         "mpc_align_trace": (i32, [vp, i64, vp, i32, vp, i64, vp, vp, i64, vp]),
+        "mpc_align_cs_sizes": (i32, [vp, i32, i64, vp, vp, i64, vp, vp]),
+        "mpc_align_cs_write": (i32, [vp, i64, vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp]),
         "mpc_draft_vote": (i32, [vp, i64, vp, i32, vp, vp, i64, vp, i64, vp, vp]),
         "mpc_draft_call": (i32, [vp, vp, i64, vp, i64, vp, vp, vp]),
     }
@@ -88,6 +90,8 @@ def host_prototypes():
         "mpc_align_plan": (i32, [vp, vp, i32, dbl, i64, vp, vp, P(i32)]),
         "mpc_align_trace_host": (i32, [vp, i64, vp, i32, vp, vp, i64, i32]),
         "mpc_align_render": (i32, [vp, i64, vp, i32, vp, vp, vp, i64, vp, vp, cp, vp, i64, vp, P(i64), i32]),
+        "mpc_align_cs_sizes_host": (i32, [vp, i32, i64, vp, vp, i64, vp, i32]),
+        "mpc_align_cs_write_host": (i32, [vp, i64, vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, i32]),
         "mpc_align_last_error": _LAST_ERROR,
         "mpc_draft_vote_host": (i32, [vp, i64, vp, i32, vp, vp, i64, vp, i64, vp, i32]),
         "mpc_draft_call_host": (i32, [vp, vp, i64, vp, i64, vp]),

@@ -12,6 +12,7 @@ include/mpc_align.h has the definition.  Per batch of reads:
   trace    band DP + canonical traceback + run encoding of a launch's reads
            (K_atrace: one wave per read; or mpc_align_trace_host)
   render   end rule + PAF lines (mpc_align_render, host threads)
+(handoff.py goes on from a launch's trace to the pileup's inputs instead.)
 
 Reads stream through in batches of at most ``batch_bases`` bases, so host and
 device memory stay bounded whatever the file size.
@@ -45,18 +46,21 @@ class TraceError(AlignError):
 
 # ---- FASTA ---------------------------------------------------------------------
 
-def fasta_records(path):
+def fasta_records(path, headers=False):
     """(name, sequence) of every record, in file order: the name is the header
     up to the first whitespace, the sequence its lines right-stripped and
-    joined.  A sequence byte that is not an ASCII letter is refused."""
-    name, parts = None, []
+    joined.  A sequence byte that is not an ASCII letter is refused.
+    ``headers``: (name, sequence, header), the header line right-stripped,
+    without its '>' (what the consensus parser takes for the name)."""
+    name, parts, whole = None, [], b""
+    rec = (lambda: (name, b"".join(parts), whole)) if headers else (lambda: (name, b"".join(parts)))
     with open(path, "rb") as f:
         for no, line in enumerate(f, 1):
             if line.startswith(b">"):
                 if name is not None:
-                    yield name, b"".join(parts)
+                    yield rec()
                 head = line[1:].split(None, 1)
-                name, parts = (head[0] if head else b""), []
+                name, parts, whole = (head[0] if head else b""), [], line.rstrip()[1:]
                 continue
             line = line.rstrip()
             if not line:
@@ -67,7 +71,7 @@ def fasta_records(path):
                 raise AlignError("{}: line {}: a sequence line may hold ASCII letters only".format(path, no))
             parts.append(line)
     if name is not None:
-        yield name, b"".join(parts)
+        yield rec()
 
 
 def read_target(path):
@@ -81,11 +85,12 @@ def read_target(path):
     return name, seq
 
 
-def read_batches(path, batch_bases=DEFAULT_BATCH_BASES):
+def read_batches(path, batch_bases=DEFAULT_BATCH_BASES, headers=False):
     """Lists of (name, sequence) holding at most ``batch_bases`` bases each (at
-    least one read), reads of unsupported length included."""
+    least one read), reads of unsupported length included (``headers``: as for
+    fasta_records)."""
     batch, bases = [], 0
-    for rec in fasta_records(path):
+    for rec in fasta_records(path, headers):
         if batch and bases + len(rec[1]) > batch_bases:
             yield batch
             batch, bases = [], 0
@@ -287,39 +292,64 @@ class Launches:
             yield reads, jobs, out, runs, kept or None
 
 
+class BatchLoop:
+    """One batch of records ((name, sequence, ...) tuples) against a target: the
+    Launches of its reads of supported length, and the summary rule, stated
+    once for align_records and handoff.feed.  ``counts`` starts with reads,
+    skipped_length and unmapped_by_distance; iterating gives what Launches
+    gives (a TraceError comes out as the AlignError that names the read) and
+    drops the blob's device copy at the end; ``count`` adds one launch's reads
+    once the caller knows which of them got a line.  ``keep[r]`` is the record
+    of read r, ``names[r]`` its name."""
+
+    def __init__(self, target, records, device=0, max_error=0.2, workspace_bytes=DEFAULT_WORKSPACE, threads=0,
+                 workspace=None, keep_device=False):
+        self.counts = dict.fromkeys(SUMMARY_FIELDS, 0)
+        self.counts["reads"] = len(records)
+        self.keep = [k for k, rec in enumerate(records) if 1 <= len(rec[1]) <= MAX_QUERY]
+        self.counts["skipped_length"] = len(records) - len(self.keep)
+        self.names = [records[k][0] for k in self.keep]
+        self.loop = Launches(target, [records[k][1] for k in self.keep], device, max_error, workspace_bytes, threads,
+                             workspace, keep_device)
+        self.pk, self.plan = self.loop.pk, self.loop.plan
+        self.counts["unmapped_by_distance"] = int((self.plan[:, 1] == 0).sum()) if len(self.keep) else 0
+        self.launches = len(self.loop.cuts) - 1
+
+    def __iter__(self):
+        try:
+            yield from self.loop
+        except TraceError as e:
+            raise AlignError("read {!r}: the band DP does not reproduce the scan's distance (status {})".format(
+                self.names[e.read].decode(errors="replace"), e.status))
+        self.pk.d_seq = None
+
+    def count(self, reads, wrote):
+        """One launch: ``wrote[k]`` says whether read reads[k] got a PAF line."""
+        minus = self.plan[reads, 0] != 0
+        self.counts["mapped"] += int(wrote.sum())
+        self.counts["minus"] += int((wrote & minus).sum())
+        self.counts["plus"] += int((wrote & ~minus).sum())
+        self.counts["unmapped_no_match"] += int((~wrote).sum())
+        return minus
+
+
 def align_records(target, tname, records, device=0, max_error=0.2, workspace_bytes=DEFAULT_WORKSPACE, threads=0,
                   workspace=None, detail=False):
     """One batch: dict(paf=bytes, counts=dict over SUMMARY_FIELDS, launches=int)
     of the (name, sequence) records, in order.  ``detail``: also plan, scan and
     per read the trace row and runs (tests)."""
-    counts = dict.fromkeys(SUMMARY_FIELDS, 0)
-    counts["reads"] = len(records)
-    keep = [k for k, (_, s) in enumerate(records) if 1 <= len(s) <= MAX_QUERY]
-    counts["skipped_length"] = len(records) - len(keep)
-    names = [records[k][0] for k in keep]
-    loop = Launches(target, [records[k][1] for k in keep], device, max_error, workspace_bytes, threads, workspace)
+    loop = BatchLoop(target, records, device, max_error, workspace_bytes, threads, workspace)
     pk, pl = loop.pk, loop.plan
-    counts["unmapped_by_distance"] = int((pl[:, 1] == 0).sum()) if len(keep) else 0
-    parts, det = [], dict(kept=keep, scan=loop.scan, plan=pl, cuts=loop.cuts, out={}, runs={})
-    try:
-        for reads, jobs, out, runs, _ in loop:
-            text, line_len = render(pk.seq, jobs, pl[reads, 0], out, runs, [names[r] for r in reads], tname, threads)
-            parts.append(text)
-            wrote = line_len > 0
-            minus = pl[reads, 0] != 0
-            counts["mapped"] += int(wrote.sum())
-            counts["minus"] += int((wrote & minus).sum())
-            counts["plus"] += int((wrote & ~minus).sum())
-            counts["unmapped_no_match"] += int((~wrote).sum())
-            if detail:
-                for k, r in enumerate(reads):
-                    det["out"][r] = out[k].copy()
-                    det["runs"][r] = runs[jobs[k, 7]: jobs[k, 7] + out[k, 6]].copy()
-    except TraceError as e:
-        raise AlignError("read {!r}: the band DP does not reproduce the scan's distance (status {})".format(
-            names[e.read].decode(errors="replace"), e.status))
-    pk.d_seq = None
-    res = dict(paf=b"".join(parts), counts=counts, launches=len(loop.cuts) - 1)
+    parts, det = [], dict(kept=loop.keep, scan=loop.loop.scan, plan=pl, cuts=loop.loop.cuts, out={}, runs={})
+    for reads, jobs, out, runs, _ in loop:
+        text, line_len = render(pk.seq, jobs, pl[reads, 0], out, runs, [loop.names[r] for r in reads], tname, threads)
+        parts.append(text)
+        loop.count(reads, line_len > 0)
+        if detail:
+            for k, r in enumerate(reads):
+                det["out"][r] = out[k].copy()
+                det["runs"][r] = runs[jobs[k, 7]: jobs[k, 7] + out[k, 6]].copy()
+    res = dict(paf=b"".join(parts), counts=loop.counts, launches=loop.launches)
     if detail:
         res["detail"] = det
     return res

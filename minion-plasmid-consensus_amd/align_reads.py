@@ -35,22 +35,12 @@ statprint = _cli.statprint
 TITLE = "Align Reads"
 
 
-def _fraction(text):
-    try:
-        v = float(text)
-    except ValueError:
-        v = -1.0
-    if not v >= 0:
-        raise argparse.ArgumentTypeError("a number >= 0")
-    return v
-
-
 def build_parser():
     p = argparse.ArgumentParser(description=TITLE)
     p.add_argument("--ref", required=True, help="Assembly fasta (exactly one record)")
     p.add_argument("--reads", required=True, help="Reads fasta")
     p.add_argument("--paf", required=True, help="PAF output file")
-    p.add_argument("--max-error", type=_fraction, default=0.2, help="Largest distance of a mapped read, as a fraction of its length")
+    p.add_argument("--max-error", type=_cli.fraction_arg, default=0.2, help="Largest distance of a mapped read, as a fraction of its length")
     p.add_argument("--summary", help="Summary output file (TSV)")
     p.add_argument("--device", type=_cli.device_arg, default=0, help="HIP device index, or 'cpu' for the host path")
     return p

@@ -5,6 +5,9 @@
 //                           the CPU checker of K_atrace, the timing baseline,
 //                           --device cpu
 //   mpc_align_render        end rule + PAF lines of a batch
+//   mpc_align_cs_sizes_host, mpc_align_cs_write_host
+//                           the pileup's inputs of a traced launch (the handoff):
+//                           the CPU checker of K_acslen and K_acswrite
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -27,37 +30,16 @@ constexpr int kOk = 0;  // MPC_OK of mpc.h
 
 thread_local mpc_host::LastError g_aerr;
 
-inline char lower(uint8_t c) { return (char)((c >= 'A' && c <= 'Z') ? c + 32 : c); }
-
 void put_int(std::string& s, int64_t v) { s += std::to_string(v); }
 
 // One read's PAF line (empty: no '=' op).
 void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool minus, const int32_t* o, const int32_t* runs,
                 const char* name, size_t name_len, const char* tname, std::string& line) {
   const int64_t m = job[1], n = job[3], end = job[5];
-  const int32_t n_runs = o[6];
-  // runs are end -> start: the kept span is [first, last] in that order between the outermost '=' runs
-  int32_t first = 0, last = n_runs - 1;
-  int64_t b_q = 0, b_t = 0, a_q = 0, a_t = 0;  // dropped read / target bases: trailing (b), leading (a)
-  while (first < n_runs && run_op(runs[first]) != kOpEq) {
-    const int64_t len = run_len(runs[first]), op = run_op(runs[first]);
-    if (op != kOpI) b_q += len;
-    if (op != kOpD) b_t += len;
-    ++first;
-  }
-  if (first == n_runs) return;
-  while (run_op(runs[last]) != kOpEq) {
-    const int64_t len = run_len(runs[last]), op = run_op(runs[last]);
-    if (op != kOpI) a_q += len;
-    if (op != kOpD) a_t += len;
-    --last;
-  }
-  const int64_t ts = o[1] + a_t, te = end - b_t;
-  int64_t n_eq = 0, n_ops = 0;
-  for (int32_t k = first; k <= last; ++k) {
-    n_ops += run_len(runs[k]);
-    if (run_op(runs[k]) == kOpEq) n_eq += run_len(runs[k]);
-  }
+  // runs are end -> start: the kept span between the outermost '=' runs (end_rule, mpc_bandtrace.h)
+  EndRule e;
+  if (!end_rule(runs, o[6], e)) return;
+  const int64_t a_q = e.a_q, b_q = e.b_q, ts = o[1] + e.a_t, te = end - e.b_t, n_eq = e.n_eq, n_ops = e.n_ops;
   line.append(name, name_len);
   line += '\t'; put_int(line, m);
   line += '\t'; put_int(line, minus ? b_q : a_q);
@@ -71,28 +53,14 @@ void render_one(const uint8_t* q, const uint8_t* t, const int64_t* job, bool min
   line += '\t'; put_int(line, n_ops);
   line += "\t255\tNM:i:"; put_int(line, n_ops - n_eq);
   line += "\tcs:Z:";
+  size_t at = line.size();
+  line.resize(at + (size_t)e.cs_bytes);
   int64_t i = a_q, j = ts;
-  for (int32_t k = last; k >= first; --k) {
-    const int64_t len = run_len(runs[k]);
-    switch (run_op(runs[k])) {
-      case kOpEq:
-        line += ':'; put_int(line, len);
-        i += len; j += len;
-        break;
-      case kOpX:
-        for (int64_t x = 0; x < len; ++x) { line += '*'; line += lower(t[j + x]); line += lower(q[i + x]); }
-        i += len; j += len;
-        break;
-      case kOpD:  // a read base missing from the target: an insertion
-        line += '+';
-        for (int64_t x = 0; x < len; ++x) line += lower(q[i + x]);
-        i += len;
-        break;
-      default:  // an extra target base: a deletion
-        line += '-';
-        for (int64_t x = 0; x < len; ++x) line += lower(t[j + x]);
-        j += len;
-    }
+  for (int32_t k = e.last; k >= e.first; --k) {
+    put_run_cs((uint8_t*)&line[at], runs[k], q, i, t, j);
+    at += (size_t)run_cs_bytes(runs[k]);
+    i += run_read_bases(runs[k]);
+    j += run_target_bases(runs[k]);
   }
   line += '\n';
 }
@@ -208,18 +176,11 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
     const int32_t* o = out + 8 * (int64_t)r;
     const char* bad = fault_text(check_job(j, seq_bytes, runs_cap));
     if (!bad && o[0] != MPC_ALIGN_OK) bad = "status is not MPC_ALIGN_OK";
-    if (!bad && (o[6] < 0 || o[6] > 2 * j[4] + 1 || o[1] < 0 || o[1] > j[5])) bad = "trace output outside its bounds";
+    if (!bad && check_traced(j, o)) bad = "trace output outside its bounds";
     if (!bad && name_off[r + 1] < name_off[r]) bad = "name offsets descend";
-    if (bad) return g_aerr.fail("mpc_align_render: read " + std::to_string(r) + ": " + bad);
     // the runs must walk exactly the read and the target span (they index both sequences)
-    int64_t qn = 0, tn = 0;
-    for (int32_t k = 0; k < o[6]; ++k) {
-      const int64_t len = run_len(runs[j[7] + k]), op = run_op(runs[j[7] + k]);
-      if (len < 1) { qn = -1; break; }
-      if (op != kOpI) qn += len;
-      if (op != kOpD) tn += len;
-    }
-    if (qn != j[1] || tn != j[5] - o[1]) return g_aerr.fail("mpc_align_render: read " + std::to_string(r) + ": runs do not span the read");
+    if (!bad) bad = fault_text(check_walk(j, o, runs + j[7]));
+    if (bad) return g_aerr.fail("mpc_align_render: read " + std::to_string(r) + ": " + bad);
   }
   // contiguous shares of reads per thread, joined in order
   const int nt = clamp_threads(threads, n_jobs);
@@ -244,5 +205,100 @@ extern "C" int mpc_align_render(const uint8_t* seq, int64_t seq_bytes, const int
     std::memcpy(buf + at, s.data(), s.size());
     at += (int64_t)s.size();
   }
+  return kOk;
+}
+
+// ---- the handoff to the pileup: the host twins of K_acslen and K_acswrite ------
+namespace {
+
+// the size row of one traced read (checked by check_traced and check_walk)
+void size_row(const int64_t* j, const int32_t* o, const int32_t* runs, int64_t* z) {
+  EndRule e;
+  for (int k = 0; k < 8; ++k) z[k] = 0;
+  if (!end_rule(runs, o[6], e)) return;
+  z[0] = 1; z[1] = 2 + e.cs_bytes; z[2] = e.a_q; z[3] = e.b_q;
+  z[4] = o[1] + e.a_t; z[5] = j[5] - e.b_t; z[6] = e.n_eq; z[7] = e.n_ops;
+}
+
+// 0, or why read r's job, trace row or runs are refused
+int check_read(const int64_t* j, const int32_t* o, const int32_t* runs, int64_t seq_bytes, int64_t runs_cap) {
+  if (const int bad = check_job(j, seq_bytes, runs_cap)) return bad;
+  if (const int bad = check_traced(j, o)) return bad;
+  return check_walk(j, o, runs + j[7]);
+}
+
+}  // namespace
+
+extern "C" int mpc_align_cs_sizes_host(const int64_t* jobs, int32_t n_jobs, int64_t seq_bytes, const int32_t* out,
+                                       const int32_t* runs, int64_t runs_cap, int64_t* sizes, int threads) {
+  if (n_jobs < 0) return g_aerr.fail("mpc_align_cs_sizes_host: n_jobs < 0");
+  if (n_jobs == 0) return kOk;
+  if (!jobs || !out || !runs || !sizes) return g_aerr.fail("mpc_align_cs_sizes_host: null pointer");
+  for (int32_t r = 0; r < n_jobs; ++r)
+    if (const int bad = check_read(jobs + 8 * (int64_t)r, out + 8 * (int64_t)r, runs, seq_bytes, runs_cap))
+      return g_aerr.fail("mpc_align_cs_sizes_host: read " + std::to_string(r) + ": " + fault_text(bad));
+  const int nt = clamp_threads(threads, n_jobs);
+  std::atomic<int32_t> next{0};
+  mpc_host::parallel(nt, [&](int) {
+    for (int32_t r; (r = next.fetch_add(64)) < n_jobs;)
+      for (int32_t k = r; k < std::min(n_jobs, r + 64); ++k) {
+        const int64_t* j = jobs + 8 * (int64_t)k;
+        size_row(j, out + 8 * (int64_t)k, runs + j[7], sizes + 8 * (int64_t)k);
+      }
+  });
+  return kOk;
+}
+
+extern "C" int mpc_align_cs_write_host(const uint8_t* seq, int64_t seq_bytes, const int64_t* jobs, int32_t n_jobs,
+                                       const int32_t* out, const int32_t* runs, int64_t runs_cap, const int64_t* sizes,
+                                       const int64_t* place, uint8_t* cs, int64_t cs_bytes, uint8_t* up, int64_t up_bytes,
+                                       uint8_t* down, int64_t down_bytes, int threads) {
+  const char* fn = "mpc_align_cs_write_host";
+  if (n_jobs < 0) return g_aerr.fail(std::string(fn) + ": n_jobs < 0");
+  if (n_jobs == 0) return kOk;
+  if (!seq || !jobs || !out || !runs || !sizes || !place || cs_bytes < 0 || up_bytes < 0 || down_bytes < 0 ||
+      (!cs && cs_bytes > 0) || (!up && up_bytes > 0) || (!down && down_bytes > 0))
+    return g_aerr.fail(std::string(fn) + ": null pointer or negative size");
+  const int64_t cap[3] = {cs_bytes, up_bytes, down_bytes};
+  int64_t at[3] = {0, 0, 0};
+  for (int32_t r = 0; r < n_jobs; ++r) {
+    const int64_t* j = jobs + 8 * (int64_t)r;
+    const int64_t* z = sizes + 8 * (int64_t)r;
+    int bad = check_read(j, out + 8 * (int64_t)r, runs, seq_bytes, runs_cap);
+    if (!bad) {
+      int64_t own[8];
+      size_row(j, out + 8 * (int64_t)r, runs + j[7], own);
+      if (std::memcmp(own, z, sizeof(own)) != 0) bad = kSizes;
+    }
+    if (!bad) bad = check_place(j, z, place + 3 * (int64_t)r, cap, at);
+    if (bad) return g_aerr.fail(std::string(fn) + ": read " + std::to_string(r) + ": " + fault_text(bad));
+  }
+  const int nt = clamp_threads(threads, n_jobs);
+  std::atomic<int32_t> next{0};
+  mpc_host::parallel(nt, [&](int) {
+    for (int32_t r; (r = next.fetch_add(16)) < n_jobs;)
+      for (int32_t k = r; k < std::min(n_jobs, r + 16); ++k) {
+        const int64_t* j = jobs + 8 * (int64_t)k;
+        const int64_t* z = sizes + 8 * (int64_t)k;
+        const int64_t* p = place + 3 * (int64_t)k;
+        if (!z[0]) continue;
+        const uint8_t* q = seq + j[0];
+        const uint8_t* t = seq + j[2];
+        const int32_t* rn = runs + j[7];
+        EndRule e;
+        end_rule(rn, out[8 * (int64_t)k + 6], e);
+        uint8_t* dst = cs + p[0];
+        dst[0] = 'Z'; dst[1] = ':';
+        int64_t b = 2, qi = z[2], tj = z[4];
+        for (int32_t x = e.last; x >= e.first; --x) {
+          put_run_cs(dst + b, rn[x], q, qi, t, tj);
+          b += run_cs_bytes(rn[x]);
+          qi += run_read_bases(rn[x]);
+          tj += run_target_bases(rn[x]);
+        }
+        for (int64_t x = 0; x < z[2]; ++x) up[p[1] + x] = upper_ascii(q[x]);
+        for (int64_t x = 0; x < z[3]; ++x) down[p[2] + x] = upper_ascii(q[j[1] - z[3] + x]);
+      }
+  });
   return kOk;
 }

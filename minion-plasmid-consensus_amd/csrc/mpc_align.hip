@@ -4,6 +4,10 @@
 //   K_arevcomp  the reverse complements of a batch's reads, one workgroup per read
 //   K_atrace    the band trace of mpc_bandtrace.h (which describes the band, its
 //               flag bytes and the traceback), one wave64 per read
+//   K_acslen    the handoff to the pileup: what cs, flanks and target start of a
+//               traced read measure, one wave64 per read
+//   K_acswrite  "Z:" + cs and the upper-cased flanks of a kept read at its place,
+//               one wave64 per read
 //
 // K_atrace keeps ONE row of band values in LDS (W + 1 ints, updated in place:
 // row i - 1's column j - 1 is slot b, its column j is slot b + 1).  The lanes
@@ -205,8 +209,167 @@ __global__ __launch_bounds__(64) void K_atrace(const uint8_t* __restrict__ seq, 
   }
 }
 
+// ---- the handoff to the pileup (include/mpc_align.h) ----------------------------
+// What a wave learns of one traced read before anything is sized or written:
+// the job and the out row checked again, the end rule and the sums of the kept
+// span.  The lanes sit across 64 runs at a time (traceback order); a ballot
+// finds the first and the last '=' of a chunk, and DPP prefix sums of what each
+// run moves and writes (run_read_bases, run_target_bases, run_cs_bytes of
+// mpc_bandtrace.h) give the sums before the first '=' (the dropped trailing
+// ops), behind the last one (the dropped leading ops) and over everything.  A
+// run of a checked trace is at most MPC_VERIFY_MAX_QUERY long (m <= 65,536,
+// deletions <= d), so every sum of at most 2 d + 1 = 8,193 runs fits 31 bits.
+struct CsMeasure {
+  int ok, kept, first, last;  // ok 0: the job, the out row or the runs are refused
+  int m, n, cs_len, up_len, down_len, tstart, tend, n_eq, n_ops;
+  int64_t q_off, t_off, run_off;
+};
+
+__device__ __forceinline__ CsMeasure cs_measure(const int64_t* __restrict__ jb, const int32_t* __restrict__ o,
+                                                const int32_t* __restrict__ runs, const int64_t runs_cap,
+                                                const int64_t seq_bytes) {
+  const int ln = lane();
+  CsMeasure M = {};
+  const int64_t q_off = jb[0], m64 = jb[1], t_off = jb[2], n64 = jb[3], d64 = jb[4], end64 = jb[5], run_off = jb[7];
+  // restates check_job and check_traced of mpc_bandtrace.h, which the host applies before the launch
+  bool ok = m64 >= 1 && m64 <= MPC_VERIFY_MAX_QUERY && n64 >= 1 && n64 <= INT32_MAX && d64 >= 0 &&
+            d64 <= MPC_ALIGN_MAX_EDITS && end64 >= 0 && end64 <= n64;
+  ok = ok && q_off >= 0 && q_off <= seq_bytes - m64 && t_off >= 0 && t_off <= seq_bytes - n64;
+  ok = ok && run_off >= 0 && run_off <= runs_cap - (2 * d64 + 1);
+  const int status = o[0], start = o[1], n_runs = o[6];
+  ok = ok && status == MPC_ALIGN_OK && n_runs >= 0 && n_runs <= 2 * d64 + 1 && start >= 0 && start <= end64;
+  if (!ok) return M;
+  const int32_t* rn = runs + run_off;
+  int all_q = 0, all_t = 0, all_b = 0, all_l = 0;  // every run
+  int bef_q = 0, bef_t = 0, bef_b = 0, bef_l = 0;  // the runs before the first '='
+  int beh_q = 0, beh_t = 0, beh_b = 0, beh_l = 0;  // the runs behind the last '=' so far
+  int n_eq = 0, first = 0, last = -1;
+  bool found = false, bad = false;
+  for (int c0 = 0; c0 < n_runs; c0 += 64) {
+    const int k = c0 + ln;
+    const bool valid = k < n_runs;
+    const int32_t run = valid ? rn[k] : 0;
+    const bool fits = run_len(run) >= 1 && run_len(run) <= MPC_VERIFY_MAX_QUERY;
+    bad = bad || ballot(valid && !fits) != 0;
+    const bool use = valid && fits;
+    const int vq = use ? (int)run_read_bases(run) : 0, vt = use ? (int)run_target_bases(run) : 0;
+    const int vb = use ? (int)run_cs_bytes(run) : 0, vl = use ? run_len(run) : 0;
+    const bool eq = use && run_op(run) == kOpEq;
+    const uint64_t em = ballot(eq);
+    const int sq = wave_scan_i32(vq), st = wave_scan_i32(vt), sb = wave_scan_i32(vb), sl = wave_scan_i32(vl);
+    const int tq = wave_last_i32(sq), tt = wave_last_i32(st), tb = wave_last_i32(sb), tl = wave_last_i32(sl);
+    n_eq += wave_sum(eq ? vl : 0);
+    if (em != 0) {
+      const int f = __ffsll((unsigned long long)em) - 1, l = 63 - __clzll((long long)em);
+      if (!found) {  // exclusive sums at lane f
+        bef_q += __shfl(sq - vq, f, 64); bef_t += __shfl(st - vt, f, 64);
+        bef_b += __shfl(sb - vb, f, 64); bef_l += __shfl(sl - vl, f, 64);
+        first = c0 + f;
+        found = true;
+      }
+      last = c0 + l;
+      beh_q = tq - __shfl(sq, l, 64); beh_t = tt - __shfl(st, l, 64);
+      beh_b = tb - __shfl(sb, l, 64); beh_l = tl - __shfl(sl, l, 64);
+    } else if (!found) {
+      bef_q += tq; bef_t += tt; bef_b += tb; bef_l += tl;
+    } else {
+      beh_q += tq; beh_t += tt; beh_b += tb; beh_l += tl;
+    }
+    all_q += tq; all_t += tt; all_b += tb; all_l += tl;
+  }
+  // the runs walk exactly the read and the target span (check_walk)
+  if (bad || all_q != (int)m64 || all_t != (int)end64 - start) return M;
+  M.ok = 1;
+  M.m = (int)m64; M.n = (int)n64; M.q_off = q_off; M.t_off = t_off; M.run_off = run_off;
+  if (!found) return M;
+  M.kept = 1; M.first = first; M.last = last;
+  M.cs_len = 2 + all_b - bef_b - beh_b;
+  M.up_len = beh_q; M.down_len = bef_q;
+  M.tstart = start + beh_t; M.tend = (int)end64 - bef_t;
+  M.n_eq = n_eq; M.n_ops = all_l - bef_l - beh_l;
+  return M;
+}
+
+// lane k < 8 holds column k of the read's size row
+__device__ __forceinline__ int64_t size_column(const CsMeasure& M, int k) {
+  const int v[8] = {M.kept, M.cs_len, M.up_len, M.down_len, M.tstart, M.tend, M.n_eq, M.n_ops};
+  int x = v[0];
+#pragma unroll
+  for (int c = 1; c < 8; ++c) x = k == c ? v[c] : x;
+  return x;
+}
+
+// grid: one 64-thread workgroup per read
+__global__ __launch_bounds__(64) void K_acslen(const int64_t* __restrict__ jobs, const int64_t seq_bytes,
+                                               const int32_t* __restrict__ out, const int32_t* __restrict__ runs,
+                                               const int64_t runs_cap, int64_t* __restrict__ sizes) {
+  const int64_t r = blockIdx.x;
+  const CsMeasure M = cs_measure(jobs + 8 * r, out + 8 * r, runs, runs_cap, seq_bytes);
+  const int ln = lane();
+  if (ln < 8) sizes[8 * r + ln] = M.ok ? size_column(M, ln) : (ln == 0 ? -1 : 0);
+}
+
+// grid: one 64-thread workgroup per read.  The wave measures the read again,
+// and writes only when that gives the size row it was handed and the place
+// holds it.  Then it walks the kept runs forward (last -> first), one lane per
+// run: the prefix sums of (cs bytes, read bases, target bases), carried from
+// chunk to chunk, give each run its byte offset and its (i, j); the lane writes
+// its run's bytes (put_run_cs), plain byte stores; the flanks are copied by the
+// whole wave, 64 bytes at a time.
+__global__ __launch_bounds__(64) void K_acswrite(const uint8_t* __restrict__ seq, const int64_t seq_bytes,
+                                                 const int64_t* __restrict__ jobs, const int32_t* __restrict__ out,
+                                                 const int32_t* __restrict__ runs, const int64_t runs_cap,
+                                                 const int64_t* __restrict__ sizes, const int64_t* __restrict__ place,
+                                                 uint8_t* __restrict__ cs, const int64_t cs_bytes,
+                                                 uint8_t* __restrict__ up, const int64_t up_bytes,
+                                                 uint8_t* __restrict__ down, const int64_t down_bytes,
+                                                 int32_t* __restrict__ status) {
+  const int64_t r = blockIdx.x;
+  const int ln = lane();
+  const CsMeasure M = cs_measure(jobs + 8 * r, out + 8 * r, runs, runs_cap, seq_bytes);
+  const int64_t* z = sizes + 8 * r;
+  const int64_t cs_off = place[3 * r], up_off = place[3 * r + 1], down_off = place[3 * r + 2];
+  bool agree = M.ok != 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) agree = agree && z[c] == size_column(M, c);
+  // restates the bounds of check_place (mpc_bandtrace.h)
+  if (agree && M.kept)
+    agree = cs_off >= 0 && cs_off <= cs_bytes - M.cs_len && up_off >= 0 && up_off <= up_bytes - M.up_len &&
+            down_off >= 0 && down_off <= down_bytes - M.down_len && M.up_len <= M.m - M.down_len;
+  if (ln == 0) status[r] = agree ? MPC_ALIGN_OK : MPC_ALIGN_BAD_JOB;
+  if (!agree || !M.kept) return;
+  const uint8_t* q = seq + M.q_off;
+  const uint8_t* t = seq + M.t_off;
+  const int32_t* rn = runs + M.run_off;
+  uint8_t* dst = cs + cs_off;
+  if (ln == 0) { dst[0] = 'Z'; dst[1] = ':'; }
+  int bo = 2, qi = M.up_len, tj = M.tstart;
+  const int total = M.last - M.first + 1;
+  for (int p0 = 0; p0 < total; p0 += 64) {
+    const int pos = p0 + ln;
+    const bool valid = pos < total;
+    const int32_t run = valid ? rn[M.last - pos] : 0;
+    const int vb = valid ? (int)run_cs_bytes(run) : 0, vq = valid ? (int)run_read_bases(run) : 0,
+              vt = valid ? (int)run_target_bases(run) : 0;
+    const int sb = wave_scan_i32(vb), sq = wave_scan_i32(vq), st = wave_scan_i32(vt);
+    const int at = bo + sb - vb, i = qi + sq - vq, j = tj + st - vt;
+    // what the lane indexes, checked again: its bytes inside the read's slot, its bases inside the read and the target
+    if (valid && at >= 2 && at + vb <= M.cs_len && i >= 0 && i + vq <= M.m && j >= 0 && j + vt <= M.n)
+      put_run_cs(dst + at, run, q, i, t, j);
+    bo += wave_last_i32(sb); qi += wave_last_i32(sq); tj += wave_last_i32(st);
+  }
+  for (int x = ln; x < M.up_len; x += 64) up[up_off + x] = upper_ascii(q[x]);
+  const uint8_t* tail = q + (M.m - M.down_len);
+  for (int x = ln; x < M.down_len; x += 64) down[down_off + x] = upper_ascii(tail[x]);
+}
+
 using mpc_launch::hip_fail;
 using mpc_launch::read_back;
+
+// "<fn>: read r: <why>" as MPC_E_ARG
+int refuse_read(const char* fn, int32_t r, const char* why) {
+  return mpc_fail_(MPC_E_ARG, (std::string(fn) + ": read " + std::to_string(r) + ": " + why).c_str());
+}
 
 }  // namespace
 
@@ -258,5 +421,67 @@ extern "C" int mpc_align_trace(const uint8_t* d_seq, int64_t seq_bytes, const in
     if (ho[(size_t)r * 8] != MPC_ALIGN_OK)
       return mpc_fail_(MPC_ALIGN_E_SCAN, ("mpc_align_trace: read " + std::to_string(r) + ": status " +
                                           std::to_string(ho[(size_t)r * 8]) + ": the band does not give the scan's distance at (m, end)").c_str());
+  return MPC_OK;
+}
+
+extern "C" int mpc_align_cs_sizes(const int64_t* d_jobs, int32_t n_jobs, int64_t seq_bytes, const int32_t* d_out,
+                                  const int32_t* d_runs, int64_t runs_cap, int64_t* d_sizes, void* stream) {
+  const char* fn = "mpc_align_cs_sizes";
+  if (n_jobs < 0) return mpc_fail_(MPC_E_ARG, "mpc_align_cs_sizes: n_jobs < 0");
+  if (n_jobs == 0) return MPC_OK;
+  if (!d_jobs || !d_out || !d_runs || !d_sizes || seq_bytes < 0 || runs_cap < 0)
+    return mpc_fail_(MPC_E_ARG, "mpc_align_cs_sizes: null pointer or negative size");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> h;
+  std::vector<int32_t> ho;
+  if (const int rc = read_back<int64_t>(st, {{d_jobs, (size_t)n_jobs * 8}}, h, fn, "job table")) return rc;
+  if (const int rc = read_back<int32_t>(st, {{d_out, (size_t)n_jobs * 8}}, ho, fn, "trace output")) return rc;
+  for (int32_t r = 0; r < n_jobs; ++r) {
+    int bad = check_job(&h[(size_t)r * 8], seq_bytes, runs_cap);
+    if (!bad) bad = check_traced(&h[(size_t)r * 8], &ho[(size_t)r * 8]);
+    if (bad) return refuse_read(fn, r, fault_text(bad));
+  }
+  hipLaunchKernelGGL(K_acslen, dim3((unsigned)n_jobs), dim3(64), 0, st, d_jobs, seq_bytes, d_out, d_runs, runs_cap, d_sizes);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(fn, "K_acslen", e);
+  if (const int rc = read_back<int64_t>(st, {{d_sizes, (size_t)n_jobs * 8}}, h, fn, "K_acslen")) return rc;
+  for (int32_t r = 0; r < n_jobs; ++r)
+    if (h[(size_t)r * 8] < 0) return refuse_read(fn, r, fault_text(kWalk));
+  return MPC_OK;
+}
+
+extern "C" int mpc_align_cs_write(const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_jobs, int32_t n_jobs,
+                                  const int32_t* d_out, const int32_t* d_runs, int64_t runs_cap, const int64_t* d_sizes,
+                                  const int64_t* d_place, uint8_t* d_cs, int64_t cs_bytes, uint8_t* d_up, int64_t up_bytes,
+                                  uint8_t* d_down, int64_t down_bytes, int32_t* d_status, void* stream) {
+  const char* fn = "mpc_align_cs_write";
+  if (n_jobs < 0) return mpc_fail_(MPC_E_ARG, "mpc_align_cs_write: n_jobs < 0");
+  if (n_jobs == 0) return MPC_OK;
+  if (!d_seq || !d_jobs || !d_out || !d_runs || !d_sizes || !d_place || !d_status || seq_bytes < 0 || runs_cap < 0 ||
+      cs_bytes < 0 || up_bytes < 0 || down_bytes < 0 || (!d_cs && cs_bytes > 0) || (!d_up && up_bytes > 0) ||
+      (!d_down && down_bytes > 0))
+    return mpc_fail_(MPC_E_ARG, "mpc_align_cs_write: null pointer or negative size");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> h;
+  std::vector<int32_t> ho;
+  const size_t J = (size_t)n_jobs;
+  if (const int rc = read_back<int64_t>(st, {{d_jobs, J * 8}, {d_sizes, J * 8}, {d_place, J * 3}}, h, fn, "tables")) return rc;
+  if (const int rc = read_back<int32_t>(st, {{d_out, J * 8}}, ho, fn, "trace output")) return rc;
+  const int64_t cap[3] = {cs_bytes, up_bytes, down_bytes};
+  int64_t at[3] = {0, 0, 0};
+  for (int32_t r = 0; r < n_jobs; ++r) {
+    const int64_t* j = &h[(size_t)r * 8];
+    int bad = check_job(j, seq_bytes, runs_cap);
+    if (!bad) bad = check_traced(j, &ho[(size_t)r * 8]);
+    if (!bad) bad = check_place(j, &h[J * 8 + (size_t)r * 8], &h[J * 16 + (size_t)r * 3], cap, at);
+    if (bad) return refuse_read(fn, r, fault_text(bad));
+  }
+  hipLaunchKernelGGL(K_acswrite, dim3((unsigned)n_jobs), dim3(64), 0, st, d_seq, seq_bytes, d_jobs, d_out, d_runs, runs_cap,
+                     d_sizes, d_place, d_cs, cs_bytes, d_up, up_bytes, d_down, down_bytes, d_status);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(fn, "K_acswrite", e);
+  if (const int rc = read_back<int32_t>(st, {{d_status, J}}, ho, fn, "K_acswrite")) return rc;
+  for (int32_t r = 0; r < n_jobs; ++r)
+    if (ho[(size_t)r] != MPC_ALIGN_OK) return refuse_read(fn, r, fault_text(kSizes));
   return MPC_OK;
 }

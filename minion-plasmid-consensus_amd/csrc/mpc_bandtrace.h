@@ -4,8 +4,10 @@
 // tables (host entry points, and device entry points on their read-back; the
 // guards of K_vscan, K_arevcomp and K_atrace restate them in place, so that
 // their code stays what it was), and the one host band DP + canonical
-// traceback (mpc_verify_script, mpc_align_trace_host).  No HIP header: g++ and
-// hipcc both compile it.
+// traceback (mpc_verify_script, mpc_align_trace_host), and the end rule of
+// align_reads with the cs bytes of a run (host and device: render_one, the
+// handoff's host twins, K_acslen and K_acswrite).  No HIP header: g++ and hipcc
+// both compile it.
 //
 // The band (include/mpc_align.h): given the scan's (d, end), row i (1 <= i <= m)
 // holds columns j = i + (end - m) - d + b, 0 <= b < W = 2 d + 1; every optimal
@@ -59,9 +61,94 @@ MPC_HD inline int32_t pack_run(int32_t len, int32_t op) { return (len << 2) | op
 MPC_HD inline int32_t run_len(int32_t run) { return run >> 2; }
 MPC_HD inline int32_t run_op(int32_t run) { return run & 3; }
 
+// ---- the end rule and the cs bytes of a run (host and device) -----------------
+// What one run moves and writes: read bases, target bases, and its bytes in the
+// short-form cs ('=' ":<len>", 'X' "*tq" per base, 'D' an insertion "+<read
+// bases>", 'I' a deletion "-<target bases>").
+MPC_HD inline int32_t dec_digits(int64_t v) {
+  int32_t k = 1;
+  while (v >= 10) { v /= 10; ++k; }
+  return k;
+}
+MPC_HD inline int64_t run_read_bases(int32_t run) { return run_op(run) != kOpI ? run_len(run) : 0; }
+MPC_HD inline int64_t run_target_bases(int32_t run) { return run_op(run) != kOpD ? run_len(run) : 0; }
+MPC_HD inline int64_t run_cs_bytes(int32_t run) {
+  const int64_t len = run_len(run);
+  switch (run_op(run)) {
+    case kOpEq: return 1 + dec_digits(len);
+    case kOpX: return 3 * len;
+  }
+  return 1 + len;
+}
+MPC_HD inline uint8_t lower_ascii(uint8_t c) { return (uint8_t)((c >= 'A' && c <= 'Z') ? c + 32 : c); }
+MPC_HD inline uint8_t upper_ascii(uint8_t c) { return (uint8_t)((c >= 'a' && c <= 'z') ? c - 32 : c); }
+
+// The kept span of a read's runs (traceback order, end -> start): [first, last]
+// between the outermost '=' runs; what the dropped ops consumed: a_q / a_t the
+// leading read / target bases (runs behind last), b_q / b_t the trailing ones
+// (runs before first); and the sums over the kept span.  kept is false, and
+// nothing else is set, for a read with no '=' run.  The wave of K_acslen takes
+// the same sums 64 runs at a time from the same per-run functions.
+struct EndRule {
+  int32_t first, last;
+  int64_t a_q, a_t, b_q, b_t;
+  int64_t cs_bytes, n_eq, n_ops;  // of the kept span (cs_bytes without the "Z:")
+};
+MPC_HD inline bool end_rule(const int32_t* runs, int32_t n_runs, EndRule& e) {
+  e = EndRule{0, n_runs - 1, 0, 0, 0, 0, 0, 0, 0};
+  while (e.first < n_runs && run_op(runs[e.first]) != kOpEq) {
+    e.b_q += run_read_bases(runs[e.first]);
+    e.b_t += run_target_bases(runs[e.first]);
+    ++e.first;
+  }
+  if (e.first >= n_runs) return false;
+  while (run_op(runs[e.last]) != kOpEq) {
+    e.a_q += run_read_bases(runs[e.last]);
+    e.a_t += run_target_bases(runs[e.last]);
+    --e.last;
+  }
+  for (int32_t k = e.first; k <= e.last; ++k) {
+    e.n_ops += run_len(runs[k]);
+    if (run_op(runs[k]) == kOpEq) e.n_eq += run_len(runs[k]);
+    e.cs_bytes += run_cs_bytes(runs[k]);
+  }
+  return true;
+}
+
+// One run's cs bytes at dst (run_cs_bytes(run) of them), read at q[i ..] and
+// target at t[j ..]; one lane of K_acswrite, one step of the host loops.
+MPC_HD inline void put_run_cs(uint8_t* dst, int32_t run, const uint8_t* q, int64_t i, const uint8_t* t, int64_t j) {
+  const int32_t len = run_len(run);
+  q += i;
+  t += j;
+  switch (run_op(run)) {
+    case kOpEq: {
+      int32_t k = dec_digits(len);
+      dst[0] = ':';
+      for (int32_t v = len; k > 0; --k, v /= 10) dst[k] = (uint8_t)('0' + v % 10);
+      break;
+    }
+    case kOpX:
+      for (int32_t x = 0; x < len; ++x) {
+        dst[3 * x] = '*';
+        dst[3 * x + 1] = lower_ascii(t[x]);
+        dst[3 * x + 2] = lower_ascii(q[x]);
+      }
+      break;
+    case kOpD:  // a read base missing from the target: an insertion
+      dst[0] = '+';
+      for (int32_t x = 0; x < len; ++x) dst[1 + x] = lower_ascii(q[x]);
+      break;
+    default:  // an extra target base: a deletion
+      dst[0] = '-';
+      for (int32_t x = 0; x < len; ++x) dst[1 + x] = lower_ascii(t[x]);
+  }
+}
+
 // ---- the table rules (host): 0, or why the row is refused --------------------
 enum Fault : int {
-  kFine = 0, kQueryEmpty, kQueryLong, kTextLen, kOffset, kSpan, kReadLen, kTargetLen, kDistance, kEnd, kSeq, kRuns, kFlags
+  kFine = 0, kQueryEmpty, kQueryLong, kTextLen, kOffset, kSpan, kReadLen, kTargetLen, kDistance, kEnd, kSeq, kRuns, kFlags,
+  kTrace, kWalk, kSizes, kPlace
 };
 
 // behind the caller's "<entry point>: read N: " / "pair N: " (kFine: null)
@@ -79,6 +166,10 @@ inline const char* fault_text(int f) {
     case kSeq: return "sequence outside the blob";
     case kRuns: return "runs outside the run buffer";
     case kFlags: return "flag rows outside the workspace or not ascending";
+    case kTrace: return "trace output outside its bounds or status not MPC_ALIGN_OK";
+    case kWalk: return "runs do not span the read";
+    case kSizes: return "size row does not agree with the job";
+    case kPlace: return "place outside its buffer, overlapping or not ascending";
   }
   return nullptr;
 }
@@ -121,6 +212,40 @@ inline int check_job(const int64_t* j, int64_t seq_bytes, int64_t runs_cap) {
 // workspace, at or behind flag_next (the end of the previous job's rows)
 inline int check_job_flags(const int64_t* j, int64_t flags_bytes, int64_t flag_next) {
   return j[6] < flag_next || j[6] > flags_bytes - j[1] * row_pitch(j[4]) ? kFlags : kFine;
+}
+
+// out row of a traced read against its job: status, run count and start inside their bounds
+inline int check_traced(const int64_t* j, const int32_t* o) {
+  return o[0] != MPC_ALIGN_OK || o[6] < 0 || o[6] > 2 * j[4] + 1 || o[1] < 0 || o[1] > j[5] ? kTrace : kFine;
+}
+
+// the runs of a traced read walk exactly its m read bases and its target span [start, end)
+inline int check_walk(const int64_t* j, const int32_t* o, const int32_t* runs) {
+  int64_t qn = 0, tn = 0;
+  for (int32_t k = 0; k < o[6]; ++k) {
+    if (run_len(runs[k]) < 1) return kWalk;
+    qn += run_read_bases(runs[k]);
+    tn += run_target_bases(runs[k]);
+  }
+  return qn != j[1] || tn != j[5] - o[1] ? kWalk : kFine;
+}
+
+// The handoff's size row {kept, cs_len, up_len, down_len, tstart, tend, n_eq,
+// n_ops} against its job and its place {cs_off, up_off, down_off} in buffers of
+// cap[3] bytes, at or behind next[3] (the ends of the previous read's slots,
+// which the call moves on): what mpc_align_cs_write[_host] checks before it
+// writes.  A read that is not kept owns no bytes.
+inline int check_place(const int64_t* j, const int64_t* z, const int64_t* place, const int64_t* cap, int64_t* next) {
+  const int64_t m = j[1], n = j[3];
+  if (z[0] != 0 && z[0] != 1) return kSizes;
+  if (z[0] == 0) return z[1] | z[2] | z[3] ? kSizes : kFine;
+  if (z[1] < 4 || z[2] < 0 || z[3] < 0 || z[2] > m - z[3] || z[4] < 0 || z[5] < z[4] || z[5] > n) return kSizes;
+  const int64_t len[3] = {z[1], z[2], z[3]};
+  for (int k = 0; k < 3; ++k) {
+    if (place[k] < next[k] || place[k] > cap[k] - len[k]) return kPlace;
+    next[k] = place[k] + len[k];
+  }
+  return kFine;
 }
 
 // ---- the host band trace -----------------------------------------------------

@@ -40,16 +40,6 @@ statprint = _cli.statprint
 TITLE = "Draft Assembly"
 
 
-def _fraction(text):
-    try:
-        v = float(text)
-    except ValueError:
-        v = -1.0
-    if not v >= 0:
-        raise argparse.ArgumentTypeError("a number >= 0")
-    return v
-
-
 def _count(least):
     def parse(text):
         try:
@@ -70,7 +60,7 @@ def build_parser():
     p.add_argument("--sample", type=_count(0), default=500, help="Reads taken from the head of the file (0: all)")
     p.add_argument("--candidates", type=_count(1), default=8, help="Reads nearest the median length tried as the seed")
     p.add_argument("--rounds", type=_count(0), default=3, help="Most rounds of align, vote and call")
-    p.add_argument("--max-error", type=_fraction, default=0.3, help="Largest distance of a mapped read, as a fraction of its length")
+    p.add_argument("--max-error", type=_cli.fraction_arg, default=0.3, help="Largest distance of a mapped read, as a fraction of its length")
     p.add_argument("--orient-to", help="Fasta (one record) whose strand the sense output takes")
     p.add_argument("--report", help="Report output file (key<TAB>value)")
     p.add_argument("--device", type=_cli.device_arg, default=0, help="HIP device index, or 'cpu' for the host path")

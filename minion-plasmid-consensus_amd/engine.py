@@ -319,20 +319,8 @@ class Batch:
         work is split by cs bytes (mpc.h h_cs_off); False splits by read count.
         ``parse_cus``: CUs the parse grid is sized for (0: all; mpc.h parse_cus),
         fewer when other batches are in flight beside this one."""
-        torch = _torch()
-        if not torch.cuda.is_available():
-            raise MpcError("no HIP device visible (the pileup path has no CPU fallback)")
-        self.device = torch.device("cuda", device)
-        S = len(samples)
-        self.n_samples = S
-        self.ref_len = np.array([len(s["ref"]) for s in samples], dtype=np.int64)
-        counts = np.array([len(s["tstart"]) for s in samples], dtype=np.int64)
-        self.read_begin = _read_begin(counts)
-        self.n_reads = int(self.read_begin[-1])
-        self.read_offset = int(read_offset)
-        self.n_reads_global = int(n_reads_global if n_reads_global is not None else self.n_reads)
-        self.shard, self.n_shards = int(shard), int(n_shards)
-        self.parse_cus = int(parse_cus)
+        torch = self._shape(samples, device, read_offset, n_reads_global, shard, n_shards, parse_cus)
+        S, counts = self.n_samples, np.diff(self.read_begin)
 
         def cat_bytes(key, offkey):
             if S == 1:  # one sample: its buffer as is (no copy of a GB of cs)
@@ -354,33 +342,103 @@ class Batch:
         cs, cs_off = cat_bytes("cs", "cs_off")
         up, up_off = cat_bytes("up", "up_off")
         dn, dn_off = cat_bytes("down", "down_off")
+        tstart = self._tables(samples, cs_off, up_off, dn_off, balance_bytes)
+        # (a shard of several: dist.ShardedPileup replaces neg_reads and neg_cs_bytes by
+        # the totals over all shards before it plans, mpc.h)
+        self.aligned_bases = int(sum(int(np.asarray(s.get("aligned", [0])).sum()) for s in samples))
+        dev = self._put
+        self.t.update(cs=dev(cs, CS_PAD), up=dev(up, FLANK_PAD), down=dev(dn, FLANK_PAD))
+
+    def _shape(self, samples, device, read_offset=0, n_reads_global=None, shard=0, n_shards=1, parse_cus=0):
+        """The counts of a launch over ``samples`` (each with ref and tstart); returns torch."""
+        torch = _torch()
+        if not torch.cuda.is_available():
+            raise MpcError("no HIP device visible (the pileup path has no CPU fallback)")
+        self.device = torch.device("cuda", device)
+        self.n_samples = len(samples)
+        self.ref_len = np.array([len(s["ref"]) for s in samples], dtype=np.int64)
+        self.read_begin = _read_begin(np.array([len(s["tstart"]) for s in samples], dtype=np.int64))
+        self.n_reads = int(self.read_begin[-1])
+        self.read_offset = int(read_offset)
+        self.n_reads_global = int(n_reads_global if n_reads_global is not None else self.n_reads)
+        self.shard, self.n_shards = int(shard), int(n_shards)
+        self.parse_cus = int(parse_cus)
+        return torch
+
+    def _put(self, a, pad=0):
+        return _native.h2d(_torch(), self.device, a, pad, floor=16)
+
+    def _tables(self, samples, cs_off, up_off, dn_off, balance_bytes):
+        """What Plan reads beside the three byte buffers, from the samples' host
+        arrays and the launch's offsets (each from 0, n_reads + 1 entries): the
+        host fields, and in self.t the device tables (ref, ref_off, the offsets,
+        tstart, sample).  Returns the launch's tstart."""
         refs = [np.asarray(s["ref"], dtype=np.uint8) for s in samples]
         ref = np.concatenate(refs) if refs else np.zeros(0, np.uint8)
         ref_off = np.concatenate([[0], np.cumsum([len(r) for r in refs])]).astype(np.int64)
-        tstart = np.concatenate([np.asarray(s["tstart"], dtype=np.int64) for s in samples])
+        tstart = np.concatenate([np.asarray(s["tstart"], dtype=np.int64) for s in samples]) if samples else np.zeros(0, np.int64)
         if len(tstart) and (tstart.min() < -(2 ** 31) or tstart.max() >= 2 ** 31):
             raise MpcError("target start out of int32 range")
-        sample = np.repeat(np.arange(S, dtype=np.int32), counts)
+        sample = np.repeat(np.arange(self.n_samples, dtype=np.int32), np.diff(self.read_begin))
         self.cs_bytes = int(cs_off[-1])
         # reads with a negative target start (Python's negative wrap, mpc.h): they
         # size the plan's list of strings written into wrapped odd positions
         neg = tstart < 0
         self.neg_reads = int(neg.sum())
         self.neg_cs_bytes = int((cs_off[1:] - cs_off[:-1])[neg].sum()) if self.neg_reads else 0
-        # (a shard of several: dist.ShardedPileup replaces both by the totals over
-        # all shards before it plans, mpc.h)
-        self.aligned_bases = int(sum(int(np.asarray(s.get("aligned", [0])).sum()) for s in samples))
-
-        dev = lambda a, pad=0: _native.h2d(torch, self.device, a, pad, floor=16)
-        self.t = dict(
-            ref=dev(ref), ref_off=dev(ref_off), cs=dev(cs, CS_PAD), cs_off=dev(cs_off),
-            tstart=dev(tstart.astype(np.int32)), up=dev(up, FLANK_PAD), up_off=dev(up_off),
-            down=dev(dn, FLANK_PAD), down_off=dev(dn_off), sample=dev(sample),
-        )
+        dev = self._put
+        self.t = dict(ref=dev(ref), ref_off=dev(ref_off), cs_off=dev(cs_off), tstart=dev(tstart.astype(np.int32)),
+                      up_off=dev(up_off), down_off=dev(dn_off), sample=dev(sample))
         self.h_cs_off = cs_off
         self.balance_bytes = bool(balance_bytes)
         self.max_flank = int(max((np.diff(up_off).max() if len(up_off) > 1 else 0),
                                  (np.diff(dn_off).max() if len(dn_off) > 1 else 0)))
+        return tstart
+
+    @classmethod
+    def from_device(cls, samples, device=0, balance_bytes=True, parse_cus=0):
+        """A Batch whose cs, up and down bytes are on the device already
+        (handoff.py: written there by K_acswrite).  Per sample: ``ref`` (the
+        upper-cased reference, host uint8), ``cs`` / ``up`` / ``down`` (uint8
+        tensors on ``device``), ``cs_off`` / ``up_off`` / ``down_off`` (host
+        int64, from 0, reads + 1 entries) and ``tstart`` (host).  One sample
+        whose tensors hold the readable room mpc.h asks for (CS_PAD bytes
+        behind the cs, FLANK_PAD behind the flanks) is taken as it is; otherwise
+        the samples' bytes are joined on the device into buffers with that room."""
+        self = cls.__new__(cls)
+        torch = self._shape(samples, device, parse_cus=parse_cus)
+        self.aligned_bases = 0
+
+        def cat(key, offkey, pad):
+            offs, base = [], 0
+            for s in samples:
+                o = np.asarray(s[offkey], dtype=np.int64)
+                if len(o) != len(s["tstart"]) + 1 or o[0] != 0 or (np.diff(o) < 0).any() or s[key].numel() < o[-1]:
+                    raise MpcError("Batch.from_device: {} does not hold reads + 1 ascending offsets from 0 inside {}".format(offkey, key))
+                offs.append(o[:-1] + base)
+                base += int(o[-1])
+            off = np.concatenate(offs + [np.array([base], dtype=np.int64)])
+            for s in samples:
+                if s[key].dtype != torch.uint8 or s[key].device != self.device or not s[key].is_contiguous():
+                    raise MpcError("Batch.from_device: {} must be a contiguous uint8 tensor on {}".format(key, self.device))
+            if len(samples) == 1 and samples[0][key].numel() >= max(base + pad, 16):
+                d = samples[0][key]
+            else:
+                d = torch.empty(max(base + pad, 16), dtype=torch.uint8, device=self.device)
+                at = 0
+                for s in samples:
+                    k = int(s[offkey][-1])
+                    d[at: at + k].copy_(s[key][:k])
+                    at += k
+            d[base: base + pad].zero_()
+            return d, off
+
+        cs, cs_off = cat("cs", "cs_off", CS_PAD)
+        up, up_off = cat("up", "up_off", FLANK_PAD)
+        dn, dn_off = cat("down", "down_off", FLANK_PAD)
+        self._tables(samples, cs_off, up_off, dn_off, balance_bytes)
+        self.t.update(cs=cs, up=up, down=dn)
+        return self
 
     def c_input(self):
         inp = _host_input(self.ref_len, self.read_begin, self.cs_bytes, self.h_cs_off if self.balance_bytes else None,
@@ -505,7 +563,13 @@ class Plan:
 def pileup(samples, mdf, gtf, device=0, row_cap=None):
     """One-shot helper: samples (packed dicts) -> per-sample call dicts.
     Re-plans once if the row capacity estimate was too small (Runner.step)."""
-    runner = Runner(samples, device, row_cap)
+    return pileup_batch(Batch(samples, device=device), mdf, gtf, row_cap)
+
+
+def pileup_batch(batch, mdf, gtf, row_cap=None):
+    """pileup() of a Batch made already (Batch.from_device: inputs that never
+    were on the host): the same Runner, the same one re-plan, the same fetch."""
+    runner = Runner(None, row_cap=row_cap, batch=batch)
     runner.step(mdf, gtf)
     res = runner.fetch()
     _torch().cuda.synchronize(runner.batch.device)
@@ -514,10 +578,11 @@ def pileup(samples, mdf, gtf, device=0, row_cap=None):
 
 class Runner:
     """Repeated pileups over one device-resident Batch (bench / serving loop).
-    The first step sizes the row buffers exactly (re-plans once if needed)."""
+    The first step sizes the row buffers exactly (re-plans once if needed).
+    ``batch``: a Batch made already, instead of ``samples``."""
 
-    def __init__(self, samples, device=0, row_cap=None, parse_cus=0):
-        self.batch = Batch(samples, device=device, parse_cus=parse_cus)
+    def __init__(self, samples, device=0, row_cap=None, parse_cus=0, batch=None):
+        self.batch = batch if batch is not None else Batch(samples, device=device, parse_cus=parse_cus)
         self.plan = Plan(self.batch, row_cap)
         self._sized = False
 
